@@ -16,7 +16,7 @@ smoke: build
 	$(PY) -c "import __graft_entry__ as g; g.smoke()"
 
 bench: build      ## one JSON line: proofs/s on the 2^20 stwo configuration, roofline, e2e, cpu_baseline
-	$(PY) bench.py
+	$(PY) bench.py --full
 
 clean:
 	$(MAKE) -C stark-symphony_amd/csrc clean

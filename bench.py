@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the batch STARK verifier hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it builds the resident batch, runs the W warm-up steps, times the
+K steps, writes the last step's outputs if `--dump-outputs DIR` is given (the per-proof status words and the accept count of
+the slot the last timed step ran on, as DIR/status.npy and DIR/accepted.npy in float64; the inputs are seeded, so two builds
+can be compared output for output) and prints the result line.  `--full` adds everything else the line can carry: the kernels'
+own durations from a separate non-overlapping pass and the `roofline` / `alu_roofline` / `kernels_ms_per_step` sections built
+on them, the text / records -> verdict figures (`e2e`) and the CPU baseline (`cpu_baseline`, `gpu_over_cpu`).
 
 One process per GPU (for N > 1 launched by torch.distributed.run; RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* come from the environment).  A "step" verifies one batch of stwo
@@ -17,9 +24,10 @@ on the one GPU at N = 1.  `--scaling weak`: every rank owns its own `--proofs-pe
 Submission (round 6): K steps are K passes of the HEAD / TAIL pipeline (verifier.Pipeline) with the TAIL halves
 alternating over two streams -- three, with four passes in flight, when a rank's share is below 32 768 proofs -- so that
 the Merkle stage of consecutive passes overlaps.  `value` and `ms_per_step` come from that timed region; a kernel's
-duration is not its own under overlap, so the durations behind `roofline` / `alu_roofline.frac` are measured by HIP events
+duration is not its own under overlap, so the durations behind `roofline` / `alu_roofline.frac` are measured (with `--full`) by HIP events
 in a pass through a ONE-slot pipeline right after it, where nothing overlaps (`roofline.durations_from`), and `roofline.launch_period_ms` /
-`alu_roofline.frac_of_step` give the timed region's own figures beside them.  `--tail-streams 1` is round 5's submission.
+`alu_roofline.frac_of_step` give the timed region's own figures beside them.  `--tail-streams 1` is round 5's submission: nothing overlaps
+there, and `--full` takes the durations in the timed region itself.
 
 Workloads (`--workload`):
   stwo_2p20      2^20-row wide-Fibonacci trace, blowup 2^4 (LDE 2^24), 16 queries, 19 inner FRI
@@ -537,6 +545,22 @@ def spawn_ranks(n: int) -> int:
     return 0
 
 
+DUMP_MAX_WORDS = 4 << 20  # status words written by --dump-outputs: 32 MB as float64
+
+
+def dump_outputs(out_dir: str, slot, rank: int, world: int) -> None:
+    """--dump-outputs: what the caller of the resident-batch path receives from the pass `slot` ran last -- the per-proof
+    status words (0 = ACCEPT) and the accept count -- as float64 .npy files (a u32 status word is exact there).  A batch of
+    more than DUMP_MAX_WORDS proofs is written as a fixed, seeded sample of its status words."""
+    status = slot.status()  # (waits for every stream of the device)
+    if status.size > DUMP_MAX_WORDS:
+        status = status[np.sort(np.random.default_rng(0x5EED2025).choice(status.size, DUMP_MAX_WORDS, replace=False))]
+    tag = "" if world == 1 else "_rank%d" % rank
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "status%s.npy" % tag), status.astype(np.float64))
+    np.save(os.path.join(out_dir, "accepted%s.npy" % tag), np.array([slot.accepted()], dtype=np.float64))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -551,15 +575,23 @@ def main() -> None:
                          "shape, 32768 for the smaller ones, 4096 for stark101)")
     ap.add_argument("--proofs-per-gpu", type=int, default=0,
                     help="proofs per rank and step; giving it selects --scaling weak")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the kernels' own durations in a separate "
+                         "non-overlapping pass (roofline, alu_roofline, kernels_ms_per_step), the text / records -> verdict "
+                         "figures (e2e) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed -- the per-proof status words and the accept count of the "
+                         "slot it ran on -- as DIR/status.npy and DIR/accepted.npy (float64; with several ranks every rank "
+                         "its share, DIR/status_rank<r>.npy)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="length of the CPU baseline's sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--distinct", type=int, default=64,
                     help="distinct valid proofs in the batch (made by the GPU prover; 0 = fixtures only)")
     ap.add_argument("--inflight", type=int, default=0,
                     help="batch passes in flight (one HIP stream each); 0 = auto: 3, or 4 (with three tail streams) when a rank's "
                          "share is below 32 768 stwo proofs per pass: profiles/r06_overlap_ab.txt")
     ap.add_argument("--e2e", type=int, default=4096,
-                    help="proof.json / proof.wit texts for the end-to-end (text -> verdict) figures; 0 = skip")
+                    help="proof.json / proof.wit texts for the end-to-end (text -> verdict) figures of --full; 0 = skip")
     ap.add_argument("--tail-streams", type=int, default=0,
                     help="streams the Merkle halves alternate over; 2: the Merkle stage of consecutive passes overlaps "
                          "(+7 %% at 8 192 proofs per GPU, +1.6 %% at 65 536: profiles/r06_overlap_ab.txt) and the kernel "
@@ -728,13 +760,13 @@ def main() -> None:
     # of its own; "stream": at once, on the pipeline's communication stream (Pipeline.submit).
     lazy = os.environ.get("SS_BENCH_REDUCE", "reuse") != "stream"
 
-    def step(i: int, p=None) -> None:
+    def step(i: int, p=None) -> int:
+        """-> the slot the pass runs on"""
         if not grouped:
-            (p or pipe).submit()
-        elif lazy:
-            (p or pipe).submit(on_reuse=reduce_accepts)
-        else:
-            (p or pipe).submit(reduce_accepts)
+            return (p or pipe).submit()
+        if lazy:
+            return (p or pipe).submit(on_reuse=reduce_accepts)
+        return (p or pipe).submit(reduce_accepts)
 
     def flush(p=None) -> None:
         if grouped and lazy:
@@ -773,15 +805,13 @@ def main() -> None:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            ind.submit()
+            last = ind.submit()
         ind.synchronize()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         assert all(s.accepted() == n_local for s in islots), "independent streams: not every proof accepted"
         graphed = True  # (for the reporting below: per-kernel durations come from the eager pass)
-        own_durations()
-        timing = ver.collect_timing()
-        ver.set_timing(False)
+        last_slot, isolated = islots[last], True
     elif graphed:
         # A pass over a few thousand stark101 proofs is shorter than the ~10 launches and event
         # operations that enqueue it, and too small to fill the chip: the K timed steps are replayed
@@ -800,14 +830,13 @@ def main() -> None:
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         assert all(s.accepted() == n_local for s in gslots[:S]), "graphed pass: not every proof accepted"
-        own_durations()
-        timing = ver.collect_timing()
-        ver.set_timing(False)
+        last_slot, isolated = gslots[S * (r & 1) + S - 1], True  # (the last slot of the graph replayed last)
     else:
         overlapped = timed_pipe is not pipe
         if not overlapped:
-            ver.set_timing(True)
-            ver.collect_timing()
+            if args.full:  # nothing overlaps here: the kernels' durations are taken in the timed region itself
+                ver.set_timing(True)
+                ver.collect_timing()
         else:
             for i in range(2 * nslot):
                 step(i, timed_pipe)
@@ -817,13 +846,19 @@ def main() -> None:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            step(i, timed_pipe)
+            last = step(i, timed_pipe)
         flush(timed_pipe)  # (the reduces of the last passes: inside the timed region)
         torch.cuda.synchronize()
         if grouped:
             dist.barrier()
         elapsed = time.perf_counter() - t0
-        if overlapped:  # the Merkle stages of consecutive passes overlap: their durations come from a pass where nothing does
+        # (the Merkle stages of consecutive passes overlap: their durations come from a pass where nothing does)
+        last_slot, isolated = slots[last], overlapped
+    if args.dump_outputs:  # before any further pass writes to the slots
+        dump_outputs(args.dump_outputs, last_slot, rank, world)
+    timing = {}
+    if args.full:
+        if isolated:
             own_durations()
         timing = ver.collect_timing()
         ver.set_timing(False)
@@ -837,20 +872,13 @@ def main() -> None:
     assert total_accept == job_proofs, "accept-reduce mismatch (%d of %d)" % (total_accept, job_proofs)
 
     # text / records in host memory -> verdicts, every rank its share at the same time (never `value`)
-    e2e = end_to_end(ver, proofs, args.e2e, rank, world, dist if grouped else None) if family == "stwo" and args.e2e > 0 else None
+    e2e = end_to_end(ver, proofs, args.e2e, rank, world, dist if grouped else None) \
+        if args.full and family == "stwo" and args.e2e > 0 else None
     if rank == 0:
         total = job_proofs * args.steps
         value = total / elapsed
-        k_ms, k_n = timing.get(dominant, (0.0, 0))
-        k_avg_s = (k_ms / max(k_n, 1)) * 1e-3
         executed = compr_per_proof
         if family == "stwo":
-            # Merkle stage = stwo_merkle (every chain up to the shared levels) + stwo_top (each distinct
-            # pair of the shared levels once): one duration, the sum of the two kernels' averages.
-            t_ms, t_n = timing.get("stwo_top", (0.0, 0))
-            k_avg_s += (t_ms / max(t_n, 1)) * 1e-3
-            if t_n:
-                dominant = "stwo_merkle+stwo_top"
             # compressions the kernels really execute: the reference's count minus the pairs memoised,
             # exact for this batch (from the queries of its distinct proofs)
             per_node = 1 if cfg.hash == "blake2s" else 2
@@ -860,14 +888,6 @@ def main() -> None:
                                                          0 if args.no_dedup else None)
                 saved.append((full - done) * per_node)
             executed = compr_per_proof - sum(saved) / len(saved)
-        launch_bytes = bytes_per_proof * n_local
-        traffic, valu_insts, traffic_src = pmc_profile(wname, n_local)
-        achieved = launch_bytes / k_avg_s / 1e9 if k_avg_s else 0.0
-        compr_s = executed * n_local / k_avg_s if k_avg_s else 0.0
-        alu_note = "compressions the Merkle stage executes per launch / its kernel time"
-        if graphed:  # slots overlap inside a graph: the meaningful rate is the whole job's
-            compr_s = executed * value / world
-            alu_note = "compressions executed per proof x proofs/s (graphed, overlapping slots: whole-job rate)"
         out = {
             "metric": "proofs verified/sec (batch), stwo 2^20-domain circle-STARK"
                       if family == "stwo" else "proofs verified/sec (batch), stark101",
@@ -898,56 +918,77 @@ def main() -> None:
                                                         "profiles/r04_queue_robustness.txt); e2e, cpu_baseline and the status words do not depend on it",
                        "submission": "%d independent streams, whole passes" % args.streams if streams else
                                      "hipGraph replay, independent slots" if graphed else
-                                     "eager, HEAD/TAIL pipelined" + (", Merkle halves alternating over %d streams (kernel "
-                                                                     "durations from a separate non-overlapping pass)"
-                                                                     % args.tail_streams if args.tail_streams > 1 else ""),
+                                     "eager, HEAD/TAIL pipelined" + (", Merkle halves alternating over %d streams%s"
+                                                                     % (args.tail_streams, " (kernel durations from a separate "
+                                                                        "non-overlapping pass)" if args.full else "")
+                                                                     if args.tail_streams > 1 else ""),
                        "parallelism": "proofs sharded over %d GPU(s)" % world,
                        "accept_reduce": None if not grouped else
                        ("all-reduce(SUM) of every step's accept count over %s, " % backend) +
                        ("enqueued on the slot's head stream when the slot is used again (one pipeline depth later), the last ones "
                         "flushed inside the timed region" if lazy else "at once on the pipeline's communication stream")},
             "hbm_gb_s": value * bytes_per_proof / 1e9,
-            "roofline": {"bound": "hbm", "kernel": dominant, "achieved": achieved,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel_avg_ms": k_avg_s * 1e3, "kernel_launches": k_n,
-                         # the rate the timed region itself sustains: one launch of the stage completes every ms_per_step
-                         # (below the sum of the two kernels' own durations when consecutive launches overlap)
-                         "launch_period_ms": elapsed / args.steps * 1e3,
-                         "achieved_per_launch_period": launch_bytes / (elapsed / args.steps) / 1e9,
-                         "durations_from": ("up to 20 passes through a one-slot pipeline after the timed region (HIP events on the launch "
-                                            "stream; nothing else on the chip): launches of the timed region overlap, a kernel's duration "
-                                            "there is not its own")
-                         if (streams or graphed or (family == "stwo" and args.tail_streams > 1)) else
-                         "HIP events on the launch stream, in the timed region",
-                         "algorithmic_bytes_per_launch": launch_bytes,
-                         "note": "integer-ALU bound by construction (2 SHA-256 / 1 Blake2s compression "
-                                 "per 32-byte sibling); see alu_roofline"},
-            "alu_roofline": {"hash_compressions_per_s": compr_s,
-                             "reference_equivalent_compressions_per_s":
-                                 compr_per_proof * n_local / k_avg_s if k_avg_s else 0.0,
-                             "calibrated_peak_compressions_per_s": alu_peak,
-                             "frac": compr_s / alu_peak,
-                             # the same over the WHOLE step (HEAD kernels, launch edges and all): compressions a pass executes
-                             # / ms_per_step -- what the timed region itself sustains against the calibrated roof
-                             "frac_of_step": executed * n_local / (elapsed / args.steps) / alu_peak,
-                             # the absolute figure beside the calibrated one: VALU wave-instructions the Merkle stage issues
-                             # (SQ_INSTS_VALU of the committed counter passes) x 2 cycles -- what a wave64 VALU operation
-                             # occupies a SIMD for (MI355X_MICROARCH.md) -- over SIMD-cycles at the nominal clock
-                             "issue_frac": (valu_insts * 2 / (N_SIMDS * NOMINAL_CLOCK_HZ * k_avg_s)) if valu_insts and k_avg_s else None,
-                             "issue_note": "SQ_INSTS_VALU x 2 cycles / (%d SIMDs x %.1f GHz x kernel time); the rotates and 3-input "
-                                           "adds SHA-256 is made of issue at half that rate on this chip (profiles/r01_valu_mixing.txt, "
-                                           "r03_sha_formulations.txt), which is why `frac` is taken against a measured calibration"
-                                           % (N_SIMDS, NOMINAL_CLOCK_HZ / 1e9),
-                             "note": alu_note + "; peak = tools/sha_bench.hip (registers only) on MI355X, "
-                                     "profiles/r01_sha_calibration.txt (34.7 G), re-measured in r03_sha_calibration.txt (34.4-34.6 G)"},
-            "kernels_ms_per_step": {k: v[0] / max(v[1], 1) for k, v in timing.items()},
         }
+        if args.full:  # everything built on the kernels' durations
+            k_ms, k_n = timing.get(dominant, (0.0, 0))
+            k_avg_s = (k_ms / max(k_n, 1)) * 1e-3
+            if family == "stwo":
+                # Merkle stage = stwo_merkle (every chain up to the shared levels) + stwo_top (each distinct
+                # pair of the shared levels once): one duration, the sum of the two kernels' averages.
+                t_ms, t_n = timing.get("stwo_top", (0.0, 0))
+                k_avg_s += (t_ms / max(t_n, 1)) * 1e-3
+                if t_n:
+                    dominant = "stwo_merkle+stwo_top"
+            launch_bytes = bytes_per_proof * n_local
+            traffic, valu_insts, traffic_src = pmc_profile(wname, n_local)
+            achieved = launch_bytes / k_avg_s / 1e9 if k_avg_s else 0.0
+            compr_s = executed * n_local / k_avg_s if k_avg_s else 0.0
+            alu_note = "compressions the Merkle stage executes per launch / its kernel time"
+            if graphed:  # slots overlap inside a graph: the meaningful rate is the whole job's
+                compr_s = executed * value / world
+                alu_note = "compressions executed per proof x proofs/s (graphed, overlapping slots: whole-job rate)"
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": dominant, "achieved": achieved,
+                             "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                             "traffic": traffic, "traffic_source": traffic_src,
+                             "kernel_avg_ms": k_avg_s * 1e3, "kernel_launches": k_n,
+                             # the rate the timed region itself sustains: one launch of the stage completes every ms_per_step
+                             # (below the sum of the two kernels' own durations when consecutive launches overlap)
+                             "launch_period_ms": elapsed / args.steps * 1e3,
+                             "achieved_per_launch_period": launch_bytes / (elapsed / args.steps) / 1e9,
+                             "durations_from": ("up to 20 passes through a one-slot pipeline after the timed region (HIP events on the launch "
+                                                "stream; nothing else on the chip): launches of the timed region overlap, a kernel's duration "
+                                                "there is not its own")
+                             if (streams or graphed or (family == "stwo" and args.tail_streams > 1)) else
+                             "HIP events on the launch stream, in the timed region",
+                             "algorithmic_bytes_per_launch": launch_bytes,
+                             "note": "integer-ALU bound by construction (2 SHA-256 / 1 Blake2s compression "
+                                     "per 32-byte sibling); see alu_roofline"},
+                "alu_roofline": {"hash_compressions_per_s": compr_s,
+                                 "reference_equivalent_compressions_per_s":
+                                     compr_per_proof * n_local / k_avg_s if k_avg_s else 0.0,
+                                 "calibrated_peak_compressions_per_s": alu_peak,
+                                 "frac": compr_s / alu_peak,
+                                 # the same over the WHOLE step (HEAD kernels, launch edges and all): compressions a pass executes
+                                 # / ms_per_step -- what the timed region itself sustains against the calibrated roof
+                                 "frac_of_step": executed * n_local / (elapsed / args.steps) / alu_peak,
+                                 # the absolute figure beside the calibrated one: VALU wave-instructions the Merkle stage issues
+                                 # (SQ_INSTS_VALU of the committed counter passes) x 2 cycles -- what a wave64 VALU operation
+                                 # occupies a SIMD for -- over SIMD-cycles at the nominal clock
+                                 "issue_frac": (valu_insts * 2 / (N_SIMDS * NOMINAL_CLOCK_HZ * k_avg_s)) if valu_insts and k_avg_s else None,
+                                 "issue_note": "SQ_INSTS_VALU x 2 cycles / (%d SIMDs x %.1f GHz x kernel time); the rotates and 3-input "
+                                               "adds SHA-256 is made of issue at half that rate on this chip (profiles/r01_valu_mixing.txt, "
+                                               "r03_sha_formulations.txt), which is why `frac` is taken against a measured calibration"
+                                               % (N_SIMDS, NOMINAL_CLOCK_HZ / 1e9),
+                                 "note": alu_note + "; peak = tools/sha_bench.hip (registers only) on MI355X, "
+                                         "profiles/r01_sha_calibration.txt (34.7 G), re-measured in r03_sha_calibration.txt (34.4-34.6 G)"},
+                "kernels_ms_per_step": {k: v[0] / max(v[1], 1) for k, v in timing.items()},
+            })
         if e2e is not None:
             out["e2e"] = e2e
-        elif family == "stark101" and args.e2e > 0 and world == 1:
+        elif args.full and family == "stark101" and args.e2e > 0 and world == 1:
             out["e2e"] = end_to_end_s101(ver, proofs[0], max(args.e2e, 16384))
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(family, proofs, args.cpu_seconds)
             out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
         print(json.dumps(out))

@@ -141,7 +141,13 @@ extern "C" int ss_host_register(ss_ctx *ctx, void *ptr, size_t bytes)
 {
     if (!ptr || !bytes) return set_err(SS_ERR_ARG, "null argument");
     SS_DEVICE_GUARD(ctx);
-    HIP_TRY(hipHostRegister(ptr, bytes, hipHostRegisterDefault));
+    const hipError_t e = hipHostRegister(ptr, bytes, hipHostRegisterDefault);
+    if (e != hipSuccess) {
+        // a host that does not let a process page-lock memory it already has refuses every such call; the runtime also keeps
+        // the error as the thread's last one, where the hipGetLastError() check behind the next launch would find it
+        (void)hipGetLastError();
+        return set_err(SS_ERR_HIP, "hipHostRegister failed: %s", hipGetErrorString(e));
+    }
     return SS_OK;
 }
 

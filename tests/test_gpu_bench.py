@@ -23,7 +23,7 @@ def _last_json(stdout: str) -> dict:
 
 def test_bench_single_gpu_json_contract():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "stwo_fixture",
-                        "--proofs-per-gpu", "2048", "--steps", "5", "--warmup", "1", "--cpu-seconds", "0.5"],
+                        "--proofs-per-gpu", "2048", "--steps", "5", "--warmup", "1", "--cpu-seconds", "0.5", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -37,6 +37,34 @@ def test_bench_single_gpu_json_contract():
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and "sample" in cb
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_outputs(tmp_path):
+    """Without --full the line carries the headline figure and its configuration only -- no pass for kernel durations, no
+    e2e, no CPU baseline -- and --dump-outputs writes what the last timed step computed: the status word of every proof
+    of the batch (all ACCEPT: bench.py refuses a batch with a rejected proof; what the files hold for a mixed batch is
+    tests/test_gpu_parity.py's test of bench.dump_outputs) and the accept count, as float64.  The same command a second
+    time writes the same bytes."""
+    import numpy as np
+    files = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "stwo_fixture",
+                            "--proofs-per-gpu", "2048", "--steps", "5", "--warmup", "1", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _last_json(r.stdout)
+        assert REQUIRED - {"roofline"} <= set(d) and d["steps"] == 5 and d["warmup"] == 1 and d["higher_is_better"] is True
+        assert d["unit"] == "proofs/s" and d["dtype"] == "u32"
+        assert abs(d["value"] - 2048 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        assert not {"roofline", "alu_roofline", "kernels_ms_per_step", "e2e", "cpu_baseline", "gpu_over_cpu"} & set(d)
+        assert "separate" not in d["config"]["submission"]  # (no pass of its own without --full)
+        assert sorted(os.listdir(out)) == ["accepted.npy", "status.npy"]
+        status, accepted = np.load(out / "status.npy"), np.load(out / "accepted.npy")
+        assert status.dtype == np.float64 and status.shape == (2048,) and not status.any()
+        assert accepted.dtype == np.float64 and accepted.tolist() == [2048.0]
+        files.append([(out / n).read_bytes() for n in ("accepted.npy", "status.npy")])
+    assert files[0] == files[1]
+
+
 def test_bench_two_ranks_share_one_gpu():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -45,7 +73,7 @@ def test_bench_two_ranks_share_one_gpu():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
                         "--gpus", "2", "--workload", "stwo_fixture", "--proofs-per-gpu", "512", "--steps", "4",
-                        "--warmup", "1", "--e2e", "301"], capture_output=True, text=True, timeout=900, env=env)
+                        "--warmup", "1", "--e2e", "301", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
     assert d["n_gpus"] == 2 and d["config"]["proofs_per_gpu"] == 512 and "cpu_baseline" not in d
@@ -69,7 +97,7 @@ def test_bench_spawns_its_own_ranks(n):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(SS_BENCH_SHARE_GPU="1", SS_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--workload",
-                        "stwo_fixture", "--proofs-per-gpu", "256", "--steps", "3", "--warmup", "1", "--e2e", "64"],
+                        "stwo_fixture", "--proofs-per-gpu", "256", "--steps", "3", "--warmup", "1", "--e2e", "64", "--full"],
                        capture_output=True, text=True, timeout=1200, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
@@ -177,7 +205,7 @@ def test_bench_collectives_through_rccl_with_one_rank():
     env.update(SS_BENCH_GROUP_OF_ONE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for extra in (["--batch", "4096"], ["--proofs-per-gpu", "2048", "--scaling", "weak"]):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "stwo_fixture", "--steps", "8",
-                            "--warmup", "2", "--no-cpu-baseline", "--e2e", "256"] + extra,
+                            "--warmup", "2", "--no-cpu-baseline", "--e2e", "256", "--full"] + extra,
                            capture_output=True, text=True, timeout=900, env=env)
         assert r.returncode == 0, r.stderr[-3000:]
         d = _last_json(r.stdout)
@@ -200,7 +228,7 @@ def test_rccl_two_ranks_verify_sharded_and_bench(tmp_path):
     assert r.returncode == 0 and r.stdout.count("ok:") == 2, (r.stdout[-2000:], r.stderr[-3000:])
     for extra in (["--proofs-per-gpu", "2048"], ["--batch", "4096"]):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "stwo_fixture",
-                            "--steps", "5", "--warmup", "2"] + extra, capture_output=True, text=True, timeout=900, env=env)
+                            "--steps", "5", "--warmup", "2", "--full"] + extra, capture_output=True, text=True, timeout=900, env=env)
         assert r.returncode == 0, r.stderr[-3000:]
         d = _last_json(r.stdout)
         assert d["n_gpus"] == 2 and d["config"]["proofs_per_gpu"] == 2048 and d["config"]["proofs_per_step"] == 4096
@@ -234,7 +262,7 @@ def test_two_ranks_on_one_gpu_over_nccl_or_the_documented_refusal():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(SS_BENCH_SHARE_GPU="1", SS_BENCH_BACKEND="nccl", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scaling", "strong", "--workload", "stwo_fixture",
-           "--batch", "2048", "--steps", "4", "--warmup", "1", "--e2e", "128"]
+           "--batch", "2048", "--steps", "4", "--warmup", "1", "--e2e", "128", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     if r.returncode == 0:
         d = _last_json(r.stdout)
@@ -262,7 +290,7 @@ def test_bench_stark101_small_batch_submission(how, label):
     whole passes (16 independent streams by default, hipGraph replay with --graph on) for the timed
     steps and takes the kernel durations from a pipelined pass."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "stark101", "--steps", "24",
-                        "--warmup", "2", "--no-cpu-baseline", "--graph", how], capture_output=True, text=True, timeout=600)
+                        "--warmup", "2", "--no-cpu-baseline", "--graph", how, "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     assert d["steps"] == 24 and d["config"]["proofs_per_gpu"] == 4096 and label in d["config"]["submission"]

@@ -178,10 +178,29 @@ def test_minimal_texts_and_cli(ver, tmp_path):
     assert r.returncode == 0 and r.stdout.strip().encode() == texts[0]
 
 
-def test_pinned_entry_points_give_the_staged_verdicts(ver):
-    """ss_stwo_verify_*_pinned (csrc/ss_pinned.hip): records, shared records and minimal records lying back to back in ONE
-    page-locked buffer -- torch's pinned allocator, or ordinary memory passed to ss_host_register -- are read by the DMA
-    engine directly; verdicts are those of the staged entry points on the same inputs; ordinary memory is refused."""
+def _hip_refuses_to_register():
+    """Asks the HIP runtime itself -- the one this process has loaded, not the project's library -- to page-lock one page
+    the process already has.  -> None where it does, else the runtime's words for the refusal (some hosts refuse every
+    hipHostRegister; the refusal is taken off the thread's last-error slot again, where the next launch's check would find it)."""
+    import ctypes as C
+    path = next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64.so" in line)
+    hip = C.CDLL(path)  # (the handle of the runtime that is loaded already)
+    hip.hipHostRegister.argtypes = [C.c_void_p, C.c_size_t, C.c_uint]
+    hip.hipHostUnregister.argtypes = [C.c_void_p]
+    hip.hipGetErrorString.restype = C.c_char_p
+    page = np.zeros(4096, dtype=np.uint8)
+    e = hip.hipHostRegister(page.ctypes.data, page.nbytes, 0)
+    if e == 0:
+        hip.hipHostUnregister(page.ctypes.data)
+        return None
+    hip.hipGetLastError()
+    return "hipHostRegister: %s" % hip.hipGetErrorString(e).decode()
+
+
+def _pinned_case(ver, registered):
+    """records, shared records and minimal records (the fixture + seeded corruptions) back to back in one buffer each --
+    from torch's pinned allocator, or ordinary memory then passed to ss_host_register: the *_pinned entry points give the
+    staged entry points' verdicts, and refuse the same words in pageable memory."""
     from stark_symphony_amd import binding as B
     p = fixtures()[0]
     cfg = p.cfg
@@ -198,31 +217,65 @@ def test_pinned_entry_points_give_the_staged_verdicts(ver):
             pass
     shared.append(shared[0][:40].copy())  # not a shared record at all
 
-    def flat_of(recs, pinned):
+    def flat_of(recs):
         offs = np.zeros(len(recs) + 1, dtype=np.uint64)
         offs[1:] = np.cumsum([r.size for r in recs])
-        buf = ver.pinned_buffer(int(offs[-1])) if pinned else np.zeros(int(offs[-1]), dtype=np.uint32)
+        buf = np.zeros(int(offs[-1]), dtype=np.uint32) if registered else ver.pinned_buffer(int(offs[-1]))
         buf[:] = np.concatenate(recs)
         return buf, offs
-    for pinned in (True, False):
-        f, _ = flat_of(full, pinned)
-        s, so = flat_of(shared, pinned)
-        mm, mo = flat_of(mins, pinned)
-        if not pinned:
-            with pytest.raises(B.SsError):  # pageable memory: refused, not silently staged
-                ver.verify_stwo_pinned(cfg, f)
+    f, _ = flat_of(full)
+    s, so = flat_of(shared)
+    mm, mo = flat_of(mins)
+    with pytest.raises(B.SsError):  # pageable memory: refused, not silently staged
+        ver.verify_stwo_pinned(cfg, f if registered else np.array(f))
+    if registered:
+        for a in (f, s, mm):
+            ver.register_host(a)  # (the host allows it: an error here is the library's)
+    try:
+        assert ver.verify_stwo_pinned(cfg, f).tolist() == ver.verify_stwo_records(cfg, np.stack(full)).tolist()
+        assert ver.verify_stwo_pinned(cfg, s, so, "shared").tolist() == ver.verify_stwo_shared_records(cfg, shared).tolist()
+        got = ver.verify_stwo_pinned(cfg, mm, mo, "minimal")
+        assert got.tolist() == ver.verify_stwo_minimal_records(cfg, mins).tolist()
+        assert got[0] == 0 and (got == 2).any()
+    finally:
+        if registered:
             for a in (f, s, mm):
-                ver.register_host(a)
-        try:
-            assert ver.verify_stwo_pinned(cfg, f).tolist() == ver.verify_stwo_records(cfg, np.stack(full)).tolist()
-            assert ver.verify_stwo_pinned(cfg, s, so, "shared").tolist() == ver.verify_stwo_shared_records(cfg, shared).tolist()
-            got = ver.verify_stwo_pinned(cfg, mm, mo, "minimal")
-            assert got.tolist() == ver.verify_stwo_minimal_records(cfg, mins).tolist()
-            assert got[0] == 0 and (got == 2).any()
-        finally:
-            if not pinned:
-                for a in (f, s, mm):
-                    ver.unregister_host(a)
+                ver.unregister_host(a)
+
+
+def test_pinned_entry_points_give_the_staged_verdicts(ver):
+    """ss_stwo_verify_*_pinned (csrc/ss_pinned.hip) on ordinary memory passed to ss_host_register: read by the DMA engine
+    directly, verdicts those of the staged entry points on the same inputs; before registration the memory is refused.
+    Needs a host whose HIP runtime page-locks memory a process already has; where the runtime itself refuses that, the
+    test has nothing to run on and skips, saying so (the pinned-allocator case below runs everywhere)."""
+    refusal = _hip_refuses_to_register()
+    if refusal:
+        pytest.skip("this host cannot page-lock existing memory (%s)" % refusal)
+    _pinned_case(ver, registered=True)
+
+
+def test_pinned_allocator_buffers_give_the_staged_verdicts(ver):
+    """The same inputs in buffers from torch's pinned allocator (Verifier.pinned_buffer = hipHostMalloc)."""
+    _pinned_case(ver, registered=False)
+
+
+def test_a_refused_registration_leaves_no_error_behind(ver):
+    """ss_host_register reports the runtime's refusal and takes it off the thread's last-error slot: the check behind the
+    next launch must not find it.  The refusal is the host's own where it cannot page-lock existing memory, else that of
+    registering the same array a second time."""
+    from stark_symphony_amd import binding as B
+    a = np.zeros(4096, dtype=np.uint32)
+    registered = False
+    try:
+        with pytest.raises(B.SsError, match="hipHostRegister"):
+            ver.register_host(a)
+            registered = True
+            ver.register_host(a)
+        p = fixtures()[0]
+        assert ver.verify_stwo_records(p.cfg, np.stack([verifier.stwo_record(p)])).tolist() == [0]
+    finally:
+        if registered:
+            ver.unregister_host(a)
 
 
 def test_pinned_texts_give_the_staged_verdicts(ver):

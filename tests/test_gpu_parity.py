@@ -279,6 +279,31 @@ def test_pipeline_matches_single_stream(ver, stwo_prod):
 
 
 @pytest.mark.streams
+def test_bench_dump_holds_the_status_words_of_the_last_pass_slot(ver, stwo_prod, tmp_path):
+    """bench.dump_outputs (bench.py --dump-outputs) on a batch of accepted AND rejected proofs: given the slot the last
+    submit returned, the files hold that slot's status words (the oracle-checked verdicts of verify_stwo, non-zero ones
+    included) and its accept count as float64 -- not those of the other slot, whose buffers are overwritten first."""
+    import bench
+    rng = np.random.default_rng(SEED + 13)
+    distinct = [stwo_prod] + [formats.stwo_corrupt(stwo_prod, rng)[0] for _ in range(7)]
+    batch = [distinct[i % 8] for i in range(256)]
+    ref = ver.verify_stwo(batch, cfg=stwo_prod.cfg)
+    assert (ref == 0).any() and (ref != 0).any()
+    a = ver.stwo_batch(batch)
+    pipe = verifier.Pipeline([a, a.sibling()])
+    last = [pipe.submit() for _ in range(4)][-1]
+    pipe.synchronize()
+    other = pipe.slots[1 - last]
+    other.status_dev.fill_(0x7FFFFFFF)
+    other.accept_dev.fill_(-1)
+    bench.dump_outputs(str(tmp_path / "d"), pipe.slots[last], 0, 1)
+    assert sorted(os.listdir(tmp_path / "d")) == ["accepted.npy", "status.npy"]
+    status, accepted = np.load(tmp_path / "d" / "status.npy"), np.load(tmp_path / "d" / "accepted.npy")
+    assert status.dtype == accepted.dtype == np.float64
+    assert status.tolist() == ref.astype(np.float64).tolist() and accepted.tolist() == [float((ref == 0).sum())]
+
+
+@pytest.mark.streams
 def test_pipeline_callbacks_see_every_pass_once(ver, stwo_prod):
     """Pipeline.submit(after_tail=...) / (on_reuse=...) + flush: the hook a caller hangs its accept reduce on runs exactly
     once per pass, ordered after that pass and before the slot's next one (bench.py's use: all_reduce of the count); with

@@ -22,18 +22,18 @@ python3 -c "import bench, json; json.dump({'kernel_sources_sha256': bench.kernel
 B="python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --inflight 1 --distinct 0 --e2e 0 --tail-streams 1"
 
 if want bench; then
-  python bench.py > $O/bench_default.json 2> $O/bench_default.err; ok default
+  python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; ok default
 fi
 if want configs; then
   for w in stwo_2p16 stwo_2p16_blake2s stwo_wide256 stwo_wide256_blake2s stwo_2p20_blake2s stwo_fixture; do
-    python bench.py --workload $w --steps 60 --warmup 6 --cpu-seconds 4 --e2e 1024 > $O/bench_$w.json 2> $O/bench_$w.err; ok "bench $w"
+    python bench.py --full --workload $w --steps 60 --warmup 6 --cpu-seconds 4 --e2e 1024 > $O/bench_$w.json 2> $O/bench_$w.err; ok "bench $w"
   done
-  python bench.py --steps 40 --warmup 4 --no-cpu-baseline --no-dedup --e2e 0 > $O/bench_stwo_2p20_nodedup.json 2> $O/bench_nodedup.err
-  python bench.py --proofs-per-gpu 8192 --steps 200 --warmup 6 --no-cpu-baseline --e2e 0 > $O/bench_stwo_2p20_8192.json 2> $O/bench_8192.err
-  python bench.py --proofs-per-gpu 8192 --steps 200 --warmup 6 --no-cpu-baseline --e2e 0 --tail-streams 1 --inflight 3 > $O/bench_stwo_2p20_8192_ts1.json 2>> $O/bench_8192.err
-  python bench.py --steps 40 --warmup 4 --no-cpu-baseline --e2e 0 --tail-streams 1 > $O/bench_stwo_2p20_ts1.json 2>> $O/bench_8192.err
-  python bench.py --workload stark101 --steps 1920 --warmup 6 --cpu-seconds 3 > $O/bench_stark101_4096.json 2> $O/bench_stark101.err; ok stark101
-  python bench.py --workload stark101 --proofs-per-gpu 8192 --steps 960 --warmup 6 --no-cpu-baseline --e2e 0 > $O/bench_stark101_8192.json 2>> $O/bench_stark101.err
+  python bench.py --full --steps 40 --warmup 4 --no-cpu-baseline --no-dedup --e2e 0 > $O/bench_stwo_2p20_nodedup.json 2> $O/bench_nodedup.err
+  python bench.py --full --proofs-per-gpu 8192 --steps 200 --warmup 6 --no-cpu-baseline --e2e 0 > $O/bench_stwo_2p20_8192.json 2> $O/bench_8192.err
+  python bench.py --full --proofs-per-gpu 8192 --steps 200 --warmup 6 --no-cpu-baseline --e2e 0 --tail-streams 1 --inflight 3 > $O/bench_stwo_2p20_8192_ts1.json 2>> $O/bench_8192.err
+  python bench.py --full --steps 40 --warmup 4 --no-cpu-baseline --e2e 0 --tail-streams 1 > $O/bench_stwo_2p20_ts1.json 2>> $O/bench_8192.err
+  python bench.py --full --workload stark101 --steps 1920 --warmup 6 --cpu-seconds 3 > $O/bench_stark101_4096.json 2> $O/bench_stark101.err; ok stark101
+  python bench.py --full --workload stark101 --proofs-per-gpu 8192 --steps 960 --warmup 6 --no-cpu-baseline --e2e 0 > $O/bench_stark101_8192.json 2>> $O/bench_stark101.err
 fi
 if want sha; then
   mkdir -p build
@@ -77,10 +77,10 @@ fi
 # the profiler passes last, from /tmp (rocprofv3 writes beside its working directory); the program itself after `--`
 cd /tmp; export TMPDIR=/tmp
 if want stats; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 30 --warmup 3 --no-cpu-baseline --e2e 0 > $O/stats.log 2>&1; ok stats
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --e2e 0 > $O/stats.log 2>&1; ok stats
   # the default submission overlaps consecutive launches of the Merkle stage (two tail streams): a kernel's duration in that trace is
   # not its own.  The roofline's durations come from a pass through a ONE-slot pipeline (nothing overlaps) -- this is its rocprof twin.
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_ts1 -- python3 $R/bench.py --steps 30 --warmup 3 --no-cpu-baseline --e2e 0 --tail-streams 1 --inflight 1 > $O/stats_ts1.log 2>&1; ok stats_ts1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_ts1 -- python3 $R/bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --e2e 0 --tail-streams 1 --inflight 1 > $O/stats_ts1.log 2>&1; ok stats_ts1
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_e2e -- python3 $R/tools/e2e_bench.py --n 4096 --reps 2 --fmt all > $O/stats_e2e.log 2>&1
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_prover -- python3 $R/tools/prover_bench.py 20 3 sha256 > $O/stats_prover.log 2>&1
 fi

@@ -8,7 +8,7 @@ d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])
 k=d['kernels_ms_per_step']
 print('%-44s %10.0f proofs/s  %8.3f ms/step  alu %.3f  merkle %.3f top %.3f' % (sys.argv[2], d['value'], d['ms_per_step'], d['alu_roofline']['frac'], k.get('stwo_merkle',0), k.get('stwo_top',0)))" "$@"; }
 T=$(mktemp -d)
-B="python bench.py --no-cpu-baseline --e2e 0 --distinct 16"
+B="python bench.py --full --no-cpu-baseline --e2e 0 --distinct 16"
 for rep in 1; do
 for n in 65536 8192; do
   S=$([ $n = 65536 ] && echo 40 || echo 240)

@@ -12,8 +12,8 @@ for rep in 1 2; do
 for v in default A B; do
   cp build/ab/libss_$v.so stark-symphony_amd/libss_verify.so
   for n in 8192 16384; do
-    echo -n "min_groups=$v n=$n alone:        "; python bench.py --proofs-per-gpu $n --steps 240 --warmup 6 --no-cpu-baseline --e2e 0 --distinct 16 2>/dev/null | line
-    echo -n "min_groups=$v n=$n RCCL reduce:  "; SS_BENCH_GROUP_OF_ONE=1 python bench.py --proofs-per-gpu $n --steps 240 --warmup 6 --no-cpu-baseline --e2e 0 --distinct 16 2>/dev/null | line
+    echo -n "min_groups=$v n=$n alone:        "; python bench.py --full --proofs-per-gpu $n --steps 240 --warmup 6 --no-cpu-baseline --e2e 0 --distinct 16 2>/dev/null | line
+    echo -n "min_groups=$v n=$n RCCL reduce:  "; SS_BENCH_GROUP_OF_ONE=1 python bench.py --full --proofs-per-gpu $n --steps 240 --warmup 6 --no-cpu-baseline --e2e 0 --distinct 16 2>/dev/null | line
   done
 done
 done
