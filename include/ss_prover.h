@@ -27,6 +27,9 @@
 #include <stdint.h>
 
 #include "ss_verify.h"
+/* The end of a proof without the host: transcript tail (last layer, proof of work, queries) and the decommitment
+ * written as the verifier's per-query record in device memory.                                                */
+#include "ss_prover_record.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -829,6 +829,178 @@ __global__ void p_pow_kernel(Dig digest_native, uint64_t target, uint64_t start,
     if (Hasher<HF>::pow_value(d) < target) atomicMin(best, (unsigned long long)nonce);
 }
 
+// ------------------------------------------------------------------- transcript tail on the device
+// What prover.py did on the host between the FRI commit and the decommitment (three downloads, hashlib, one upload), by ONE
+// workgroup: the channel is a dependent chain of a few compressions, so every lane carries it in registers and computes
+// the same digest -- no broadcast -- and the only data-parallel steps are the scan of the last layer and the nonce search,
+// where the lanes try consecutive nonces, one block of blockDim nonces per round.  The smallest hit of a round is taken by a
+// 64-bit min in LDS; rounds are tried in ascending order, so the first round with a hit holds the smallest nonce of all.
+constexpr uint32_t kFinishThreads = 256;
+
+template <int HF>
+__global__ void __launch_bounds__(kFinishThreads)
+p_finish_kernel(uint32_t *__restrict__ state, const uint32_t *__restrict__ last, size_t n_last, uint64_t target,
+                uint64_t span, uint32_t lde_log, uint32_t n_queries, uint32_t *__restrict__ queries,
+                uint32_t *__restrict__ nonce_out, uint32_t *__restrict__ err)
+{
+    __shared__ unsigned long long best;
+    constexpr unsigned long long kNone = ~0ull;
+    const uint32_t tid = threadIdx.x;
+    const uint4 *rows = reinterpret_cast<const uint4 *>(last);
+    const uint4 first = rows[0];
+    int differs = 0;
+    for (size_t i = tid; i < n_last; i += kFinishThreads) {
+        const uint4 v = rows[i];
+        differs |= (v.x != first.x) | (v.y != first.y) | (v.z != first.z) | (v.w != first.w);
+    }
+    Channel<HF> ch;
+#pragma unroll
+    for (int i = 0; i < 8; i++) ch.dig.v[i] = Hasher<HF>::native(state[i]);
+    ch.ctr = state[8];
+    if (tid == 0) best = kNone;
+    const int bad_layer = __syncthreads_or(differs);  // (also: every lane has read `state`, `best` is set)
+    const uint32_t lv[4] = {first.x, first.y, first.z, first.w};
+    ch.mix_values(lv);
+    unsigned long long nonce = kNone;
+    for (uint64_t base = 0; base < span; base += kFinishThreads) {
+        const uint64_t cand = base + tid;
+        if (cand < span) {
+            const uint32_t m[2] = {(uint32_t)(cand >> 32), (uint32_t)cand};
+            uint32_t d[8];
+            Hasher<HF>::template block<true, 8, 2>(ch.dig.v, m, d);
+            if (Hasher<HF>::pow_value(d) < target) atomicMin(&best, (unsigned long long)cand);
+        }
+        __syncthreads();
+        nonce = best;
+        __syncthreads();  // (nobody enters the next round's atomicMin before everybody has read this round's result)
+        if (nonce != kNone) break;
+    }
+    if (nonce != kNone) {
+        const uint32_t nv[2] = {(uint32_t)(nonce >> 32), (uint32_t)nonce};
+        ch.mix_values(nv);
+        const uint32_t mask = (uint32_t)(((uint64_t)1 << lde_log) - 1);
+        for (uint32_t got = 0; got < n_queries; got += 8) {
+            uint32_t w[8];
+            ch.draw_words(w);
+            if (tid == 0) {
+#pragma unroll
+                for (uint32_t k = 0; k < 8; k++)
+                    if (got + k < n_queries) queries[got + k] = w[k] & mask;
+            }
+        }
+        if (tid == 0) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) state[i] = Hasher<HF>::native(ch.dig.v[i]);
+            state[8] = ch.ctr;
+            nonce_out[0] = nv[0];
+            nonce_out[1] = nv[1];
+        }
+    } else if (tid < n_queries) {
+        queries[tid] = 0;  // defined positions for a decommitment already enqueued behind this kernel
+    }
+    const uint32_t bits = (bad_layer ? SS_P_ERR_LAST_LAYER : 0u) | (nonce == kNone ? SS_P_ERR_POW_SPAN : 0u);
+    if (tid == 0 && bits) atomicOr(err, bits);
+}
+
+// ---------------------------------------------------------------------- decommitment -> record
+// A proof opens (K + 3) Q authentication chains: tree `kind` (0 trace, 1 composition, 2 + l FRI layer l) at query q.
+// A chain is at most L siblings of 32 bytes that lie L different places of the tree's `levels` array and go to ONE
+// contiguous slot of the record, so a wavefront owns a chain and a lane owns half a sibling: lane 2 * level + half
+// computes its source row in registers from the query (level j of a tree of n leaves starts at row 2n - (2n >> j), the
+// sibling of position p there is (p >> j) ^ 1) and moves one uint4.  64 lanes = 32 levels >= the layout's bound of 31,
+// so the level loop runs once.  A slot is 16-byte aligned or not as a whole (siblings are 8 words apart): aligned chains
+// store uint4, the others four words.  The chain's wavefront also moves the chain's queried values (kind 0: the N trace
+// columns at q, strided over the lanes; kind 1: the 16 composition values of q's pair; FRI: the 4-word fold partner),
+// and one more workgroup writes the head and the path_len trailer, so every word of the record is written exactly once.
+// The tree descriptors (at most 34) are staged in LDS once per workgroup: the head reads them all, a chain its own.
+struct DecommitArgs {
+    uint32_t N, L, Q, K;
+    Dig const_root;  // stored words
+};
+constexpr uint32_t kDecommitThreads = 256, kDecommitChains = kDecommitThreads / 64;
+
+__device__ __forceinline__ void move16(uint32_t *dst, const uint32_t *src)
+{
+    const uint4 v = *reinterpret_cast<const uint4 *>(src);
+    if (((uintptr_t)dst & 15) == 0) {
+        *reinterpret_cast<uint4 *>(dst) = v;
+    } else {
+        dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+    }
+}
+
+__global__ void __launch_bounds__(kDecommitThreads)
+p_decommit_record_kernel(DecommitArgs a, const ss_p_tree *__restrict__ trees_dev, const uint32_t *__restrict__ samples,
+                         const uint32_t *__restrict__ fri_roots, const uint32_t *__restrict__ last,
+                         const uint32_t *__restrict__ nonce, const uint32_t *__restrict__ queries, uint32_t *__restrict__ rec)
+{
+    __shared__ ss_p_tree trees[kMaxList + 3];
+    __shared__ uint32_t qs[kMaxQueries];
+    const uint32_t tid = threadIdx.x, N = a.N, L = a.L, Q = a.Q, K = a.K, kinds = K + 3;
+    for (uint32_t i = tid; i < kinds; i += kDecommitThreads) trees[i] = trees_dev[i];
+    if (tid < Q) qs[tid] = queries[tid] & (uint32_t)(((uint64_t)1 << L) - 1);
+    __syncthreads();
+    const uint32_t oods = 4 * (N + kCp), head = 24 + oods + 8 * (K + 1) + 6;  // roots, samples, FRI roots, last layer, nonce
+    const uint32_t per_q = N + kCp + 16 * L;
+    if (blockIdx.x == gridDim.x - 1) {
+        // ---- head and trailer
+        const uint32_t *troot = trees[0].levels + (((uint64_t)2 << L) - 2) * 8;
+        const uint32_t *croot = trees[1].levels + (((uint64_t)1 << L) - 2) * 8;  // (tree over the 2^(L-1) pairs)
+        for (uint32_t w = tid; w < head; w += kDecommitThreads) {
+            uint32_t v = 0, r = w;
+            if (r < 8) {
+#pragma unroll
+                for (uint32_t k = 0; k < 8; k++)  // (a kernel argument: selected, not indexed)
+                    if (r == k) v = a.const_root.v[k];
+            }
+            else if ((r -= 8) < 8) v = troot[r];
+            else if ((r -= 8) < 8) v = croot[r];
+            else if ((r -= 8) < oods) v = samples[r];
+            else if ((r -= oods) < 8 * (K + 1)) v = fri_roots[r];
+            else if ((r -= 8 * (K + 1)) < 4) v = last[r];
+            else v = nonce[r - 4];
+            rec[w] = v;
+        }
+        uint32_t *plen = rec + stwo_record_words(N, L, Q, K) - (uint64_t)kinds * Q;
+        for (uint32_t i = tid; i < kinds * Q; i += kDecommitThreads) {
+            const uint32_t kind = i / Q;
+            plen[i] = kind < 2 ? L : L + 1 - kind;
+        }
+        return;
+    }
+    const uint32_t lane = tid & 63, chain = blockIdx.x * kDecommitChains + (tid >> 6);
+    if (chain >= kinds * Q) return;
+    const uint32_t kind = chain / Q, q = chain - kind * Q, idx = qs[q];
+    const ss_p_tree t = trees[kind];
+    // the chain's tree has 2^m leaves, the chain enters it at position p, and its sibling s is tree level s + first
+    // (composition: sibling 0 is the pair's other leaf, the same hash, and the tree over the pairs starts above it)
+    uint32_t m, p, len, *dst;
+    int first;
+    if (kind == 0) {
+        uint32_t *slot = rec + head + (size_t)q * per_q;
+        for (uint32_t c = lane; c < N; c += 64) slot[c] = t.values[((size_t)c << L) + idx];
+        m = L; p = idx; len = L; first = 0; dst = slot + N + kCp;
+    } else if (kind == 1) {
+        uint32_t *slot = rec + head + (size_t)q * per_q + N;
+        if (lane < kCp) slot[lane] = t.values[((size_t)lane << (L - 1)) + (idx >> 1)];
+        m = L - 1; p = idx >> 1; len = L; first = -1; dst = slot + kCp + 8 * L;
+    } else {
+        const uint32_t l = kind - 2;
+        len = L - 1 - l;
+        // layers 0 .. l-1 hold Q (4 + 8 (L - 1 - l')) words each
+        const uint32_t before = Q * (4 * l + 8 * (l * (L - 1) - l * (l - 1) / 2));
+        uint32_t *slot = rec + head + (size_t)Q * per_q + before + (size_t)q * (4 + 8 * len);
+        m = L - l; p = idx >> l; first = 1; dst = slot + 4;
+        if (lane == 0) move16(slot, t.values + (size_t)(p ^ 1) * 4);
+    }
+    const uint64_t two_n = (uint64_t)2 << m;
+    for (uint32_t s = lane >> 1; s < len; s += 32) {
+        const int j = (int)s + first;
+        const uint32_t *src = j < 0 ? t.leaf + (size_t)p * 8 : t.levels + (two_n - (two_n >> j) + ((p >> j) ^ 1)) * 8;
+        move16(dst + s * 8 + (lane & 1) * 4, src + (lane & 1) * 4);
+    }
+}
+
 }  // namespace ss
 
 // =============================================================================== C ABI
@@ -1135,6 +1307,46 @@ extern "C" int ss_p_pow(ss_ctx *ctx, uint32_t hash, const uint32_t digest[8], ui
     else
         hipLaunchKernelGGL(p_pow_kernel<0>, dim3(blocks_for(count)), dim3(256), 0, s, d, target, start, count,
                            (unsigned long long *)nonce_out_dev);
+    P_TRY(hipGetLastError());
+    return SS_OK;
+}
+
+extern "C" int ss_p_finish_dev(ss_ctx *ctx, uint32_t hash, uint32_t lde_log, uint32_t n_queries, uint64_t pow_target,
+                               uint64_t span, uint32_t *state_dev, const uint32_t *last_dev, size_t n_last,
+                               uint32_t *queries_out_dev, uint32_t *nonce_out_dev, uint32_t *err_dev, void *stream)
+{
+    SS_DEVICE_GUARD(ctx);
+    // (the two sizes this call depends on, by the layout's own rule; the other fields at their smallest legal values)
+    if (!stwo_cfg_ok(1, 1, lde_log, n_queries, 0, 0) || hash > 1 || !span || !state_dev || !last_dev || !n_last ||
+        !queries_out_dev || !nonce_out_dev || !err_dev)
+        return ss_internal_set_err(SS_ERR_ARG, "ss_p_finish_dev: bad argument");
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(1), dim3(kFinishThreads), 0, (hipStream_t)stream, state_dev, last_dev, n_last,
+                           pow_target, span, lde_log, n_queries, queries_out_dev, nonce_out_dev, err_dev);
+    };
+    if (hash) launch(p_finish_kernel<1>);
+    else launch(p_finish_kernel<0>);
+    P_TRY(hipGetLastError());
+    return SS_OK;
+}
+
+extern "C" int ss_p_decommit_record(ss_ctx *ctx, const ss_stwo_cfg *cfg, const ss_p_tree *trees_dev,
+                                    const uint32_t *samples_dev, const uint32_t *fri_roots_dev, const uint32_t *last_dev,
+                                    const uint32_t *nonce_dev, const uint32_t const_root[8], const uint32_t *queries_dev,
+                                    uint32_t *record_out_dev, void *stream)
+{
+    SS_DEVICE_GUARD(ctx);
+    if (!cfg || !stwo_cfg_ok(cfg->n_cols, cfg->trace_log, cfg->lde_log, cfg->n_queries, cfg->n_layers, cfg->mode) ||
+        !trees_dev || !samples_dev || !fri_roots_dev || !last_dev || !nonce_dev || !const_root || !queries_dev ||
+        !record_out_dev || ((uintptr_t)record_out_dev & 3))
+        return ss_internal_set_err(SS_ERR_ARG, "ss_p_decommit_record: bad argument");
+    DecommitArgs a;
+    a.N = cfg->n_cols; a.L = cfg->lde_log; a.Q = cfg->n_queries; a.K = cfg->n_layers;
+    for (int i = 0; i < 8; i++) a.const_root.v[i] = const_root[i];
+    const uint32_t chains = (a.K + 3) * a.Q;
+    hipLaunchKernelGGL(p_decommit_record_kernel, dim3(blocks_for(chains, kDecommitChains) + 1), dim3(kDecommitThreads), 0,
+                       (hipStream_t)stream, a, trees_dev, samples_dev, fri_roots_dev, last_dev, nonce_dev, queries_dev,
+                       record_out_dev);
     P_TRY(hipGetLastError());
     return SS_OK;
 }

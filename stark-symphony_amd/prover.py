@@ -9,7 +9,9 @@ host; everything proportional to the domain size runs in HIP kernels.
 
 Output: the reference's `proof.json` schema (format C), byte for byte equal to
 tools/stwo_prover.py -- and therefore to the reference's two fixtures
-(tests/test_gpu_prover.py).
+(tests/test_gpu_prover.py).  `prove_record` / `prove_records` give the same proof as the verifier's
+per-query record (include/ss_verify.h) written by the GPU: after the FRI commit the transcript's tail
+and the decommitment run in two kernels (include/ss_prover_record.h) and only an error word is read.
 """
 from __future__ import annotations
 
@@ -138,8 +140,11 @@ class GpuProver:
         sig("ss_p_quotients", C.c_uint32, C.c_uint32, u32p, u32p, C.c_uint32, u32p, u32p, u32p, u32p, u32p, u32p)
         sig("ss_p_fri_fold", sz, u32p, u32p, u32p, u32p)
         sig("ss_p_pow", C.c_uint32, u32p, C.c_uint64, C.c_uint64, C.c_uint64, u32p)
+        sig("ss_p_finish_dev", C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, u32p, u32p, sz, u32p, u32p, u32p)
+        sig("ss_p_decommit_record", C.POINTER(B.StwoCfg), vp, u32p, u32p, u32p, u32p, u32p, u32p, u32p)
         self._dom: Dict[int, tuple] = {}
         self._workers: list = []  # (prover, stream) of prove_many
+        self._pending = None  # (commit, record, error word) of a prove_record not yet checked
         self.timings: Dict[str, float] = {}
 
     # -- small helpers ---------------------------------------------------------------------
@@ -260,9 +265,11 @@ class GpuProver:
         return rows.reshape(-1, 8).astype(">u4").view(np.uint8).reshape(-1, 32).tolist()
 
     # -- the protocol ----------------------------------------------------------------------
-    def prove_proof(self, n_cols: int = 4, trace_log: int = 9, log_blowup: int = 4, n_queries: int = 16,
-                    pow_bits: int = 5, seed: int = 0, hash: str = "sha256"):
-        """-> formats.StwoProof (arrays; what the verifier's record is made from)."""
+    def _commit(self, n_cols: int = 4, trace_log: int = 9, log_blowup: int = 4, n_queries: int = 16,
+                pow_bits: int = 5, seed: int = 0, hash: str = "sha256"):
+        """The protocol up to and including the FRI commit, shared by prove_proof and prove_record: everything the rest
+        of a proof is made from, still on the device (trees, layers, samples, the channel state after the last fold)."""
+        import types
         torch = self.torch
         t_start = time.perf_counter()
         marks: List[Tuple[str, float]] = []
@@ -400,8 +407,19 @@ class GpuProver:
             self._call("ss_p_fri_fold_dev", size >> 1, layer.data_ptr(), itw_L[off:].data_ptr(),
                        alphas_dev[l].data_ptr(), nxt.data_ptr())
             layer = nxt
+        return types.SimpleNamespace(
+            N=N, n=n, L=L, K=K, Q=n_queries, pow_bits=pow_bits, hash=hash, hsel=hsel, ch=ch, mark=mark, marks=marks,
+            t_start=t_start, const_root=const_root, trace_root=trace_root, cp_root=cp_root, oods_trace=oods_trace,
+            oods_cp=oods_cp, samples=samples, lde=lde, cp_lde=cp_lde, trace_tree=trace_tree, pair_leaf=pair_leaf,
+            cp_tree=cp_tree, layers=layers, trees=trees, state=state, roots_dev=roots_dev, last=layer)
+
+    def _host_tail(self, c):
+        """The end of the transcript on the host: one download (channel, FRI roots, last layer), the last layer's mix,
+        the proof of work searched by ss_p_pow, the queries.  -> (roots, last, nonce, queries)"""
+        torch = self.torch
+        ch, K, L, pow_bits, hsel, mark = c.ch, c.K, c.L, c.pow_bits, c.hsel, c.mark
         g = self._Gather(self)
-        k_state, k_roots, k_last = g.take(state), g.take(roots_dev), g.take(layer)
+        k_state, k_roots, k_last = g.take(c.state), g.take(c.roots_dev), g.take(c.last)
         got = g.fetch()
         ch.digest = got[k_state][:8].astype(">u4").tobytes()
         ch.counter = int(got[k_state][8])
@@ -431,9 +449,21 @@ class GpuProver:
         # ---- queries (fri/queries.simf:29-43) and decommitment
         mask = (1 << L) - 1
         queries: List[int] = []
-        while len(queries) < n_queries:
+        while len(queries) < c.Q:
             queries += [w & mask for w in ch.draw_words()]
-        queries = queries[:n_queries]
+        return roots, last, nonce, queries[:c.Q]
+
+    def prove_proof(self, n_cols: int = 4, trace_log: int = 9, log_blowup: int = 4, n_queries: int = 16,
+                    pow_bits: int = 5, seed: int = 0, hash: str = "sha256"):
+        """-> formats.StwoProof (arrays; what the verifier's record is made from)."""
+        c = self._commit(n_cols, trace_log, log_blowup, n_queries, pow_bits, seed, hash)
+        N, n, L, K = c.N, c.n, c.L, c.K
+        size_L, half_L = 1 << L, 1 << (L - 1)
+        lde, cp_lde, trace_tree, pair_leaf, cp_tree, layers, trees = (c.lde, c.cp_lde, c.trace_tree, c.pair_leaf,
+                                                                      c.cp_tree, c.layers, c.trees)
+        const_root, trace_root, cp_root, oods_trace, oods_cp = c.const_root, c.trace_root, c.cp_root, c.oods_trace, c.oods_cp
+        mark, marks, t_start = c.mark, c.marks, c.t_start
+        roots, last, nonce, queries = self._host_tail(c)
         self.queries = list(queries)  # (of the last proof made by this call path; prove_minimal uses them)
         # every gather of the decommitment is enqueued first, then downloaded at once
         g = self._Gather(self)
@@ -477,21 +507,117 @@ class GpuProver:
         self.timings["total"] = prev - t_start
         return proof
 
+    # -- the proof as the verifier's record, in device memory ------------------------------------
+    @staticmethod
+    def config(n_cols: int = 4, trace_log: int = 9, log_blowup: int = 4, n_queries: int = 16, pow_bits: int = 5,
+               seed: int = 0, hash: str = "sha256"):
+        """The formats.StwoConfig of the proofs these arguments give: what a verifier of prove_record's output expects."""
+        from .formats import StwoConfig
+        return StwoConfig(n_cols, trace_log, trace_log + log_blowup, n_queries, trace_log - 1, pow_bits, hash)
+
+    def _decommit_record(self, c, queries_dev, nonce_dev, out) -> None:
+        # one ss_p_tree (levels, values, leaf) per tree: trace, composition, FRI layers
+        desc = [(c.trace_tree, c.lde, None), (c.cp_tree, c.cp_lde, c.pair_leaf)] + list(zip(c.trees, c.layers, [None] * (c.K + 1)))
+        trees_dev = self.torch.tensor([[t.data_ptr() if t is not None else 0 for t in row] for row in desc],
+                                      dtype=self.torch.int64).to(self.dev)
+        root = (C.c_uint32 * 8)(*np.frombuffer(c.const_root, dtype=">u4").astype(np.uint32))
+        self._call("ss_p_decommit_record", C.byref(c.cs), trees_dev.data_ptr(), c.samples.data_ptr(), c.roots_dev.data_ptr(),
+                   c.last.data_ptr(), nonce_dev.data_ptr(), root, queries_dev.data_ptr(), out.data_ptr())
+
+    def prove_record(self, out=None, pow_span: Optional[int] = None, check: bool = True, **kw):
+        """The proof of prove_proof(**kw) as the per-query record of include/ss_verify.h (verifier.stwo_record of it, word
+        for word), written by the GPU into `out`: int32[record_words] on the device, e.g. a row of a caller's
+        [n, record_words] tensor (allocated here when None; it may be uninitialised).  After the FRI commit nothing returns
+        to the host but one error word: ss_p_finish_dev ends the transcript (last layer, proof of work over the first
+        `pow_span` nonces -- default 2^min(22, pow_bits + 8), the first pass of prove_proof's search -- and queries),
+        ss_p_decommit_record gathers the record.  check=False leaves that word unread: the record is then valid once
+        check() has returned, and the caller runs no other proof on this prover before."""
+        self.check()
+        c = self._commit(**kw)
+        from .verifier import MODE_FIXTURE, stwo_cfg_struct
+        c.cs = stwo_cfg_struct(self.config(c.N, c.n, c.L - c.n, c.Q, c.pow_bits, 0, c.hash), MODE_FIXTURE)
+        words = self.lib.ss_stwo_record_words(C.byref(c.cs))
+        if out is None:
+            out = self._empty(words)
+        if out.dtype != self.torch.int32 or out.numel() != words or not out.is_contiguous() or out.device != c.state.device:
+            raise ValueError("out must be %d contiguous int32 words on the prover's device" % words)
+        span = pow_span if pow_span is not None else 1 << min(22, c.pow_bits + 8)
+        err = self._zeros(1)
+        tail = self._empty(c.Q + 2)  # queries, nonce hi, lo
+        self._call("ss_p_finish_dev", c.hsel, c.L, c.Q, c.cs.pow_target, span, c.state.data_ptr(), c.last.data_ptr(),
+                   c.last.shape[0], tail.data_ptr(), tail[c.Q:].data_ptr(), err.data_ptr())
+        self._decommit_record(c, tail, tail[c.Q:], out)
+        self._pending = (c, out, err)
+        if check:
+            self.check()
+        return out
+
+    def check(self) -> None:
+        """Waits for the last prove_record of this prover (on the current stream) and reads its error word -- the only
+        host read after the FRI commit.  SS_P_ERR_LAST_LAYER raises what prove_proof raises.  SS_P_ERR_POW_SPAN (no
+        nonce in the span) redoes the tail on the host path of prove_proof and the decommitment with the queries and
+        nonce uploaded: the same record."""
+        pending, self._pending = self._pending, None
+        if pending is None:
+            return
+        c, out, err = pending
+        bits = int(err.cpu()[0])
+        if bits & 1:
+            raise AssertionError("last FRI layer is not constant: the quotient is not low degree")
+        if bits & 2:
+            _, _, nonce, queries = self._host_tail(c)
+            tail = self.torch.from_numpy(np.array(queries + [nonce >> 32, nonce & 0xFFFFFFFF], dtype=np.uint32).view(np.int32)).to(self.dev)
+            self._decommit_record(c, tail, tail[c.Q:], out)
+            self.torch.cuda.current_stream(self.dev).synchronize()
+        c.mark("tail")
+        prev = c.t_start
+        self.timings = {}
+        for name, ts in c.marks:
+            self.timings[name] = ts - prev
+            prev = ts
+        self.timings["total"] = prev - c.t_start
+
+    def prove_records(self, seeds: Sequence[int], workers: int = 4, **kw):
+        """prove_record for every seed of `seeds` on the schedule of prove_many (the same worker streams and threads):
+        -> int32[len(seeds), record_words] on the device, row i = the record of seeds[i], every row checked and the
+        device synchronised.  ss_stwo_pack_dev / Verifier.pack_stwo_records_dev take the tensor as it is."""
+        seeds = list(seeds)
+        if not seeds:
+            return self._empty(0, 0)
+        t0 = time.perf_counter()
+        first = self.prove_record(seed=seeds[0], **kw)  # also fills the twiddle cache every worker shares
+        rows = self._empty(len(seeds), first.numel())
+        rows[0] = first
+
+        def one(gp, i):
+            gp.prove_record(out=rows[i], seed=seeds[i], **kw)
+        self._run_many(len(seeds), workers, one, t0)
+        return rows
+
     def prove_many(self, seeds: Sequence[int], workers: int = 4, **kw) -> list:
         """Proofs of the same configuration for every seed of `seeds`, `workers` of them in flight, each on its own
         HIP stream (and host thread).  A single proof leaves the GPU idle between its many dependent launches -- the
         small upper Merkle levels, the channel round trips -- and other proofs' kernels fill those gaps; nothing else
         changes, so every proof is byte-identical to `prove_proof(seed=...)`.  Returns the StwoProofs in seed order;
         `self.timings["proofs_per_s"]` is the rate of the call."""
-        import itertools
-        import threading
-        torch = self.torch
         seeds = list(seeds)
         out: list = [None] * len(seeds)
         if not seeds:
             return out
         t0 = time.perf_counter()
         out[0] = self.prove_proof(seed=seeds[0], **kw)  # also fills the twiddle cache every worker shares
+
+        def one(gp, i):
+            out[i] = gp.prove_proof(seed=seeds[i], **kw)
+        self._run_many(len(seeds), workers, one, t0)
+        return out
+
+    def _run_many(self, count: int, workers: int, one, t0: float) -> None:
+        """The schedule of prove_many / prove_records: items 1 .. count-1 (item 0 is done: it filled the twiddle cache)
+        through one(prover, i), `workers` of them in flight; t0 = when the caller began item 0."""
+        import itertools
+        import threading
+        torch = self.torch
         nxt = itertools.count(1)
         errors: list = []
 
@@ -507,12 +633,12 @@ class GpuProver:
                 with torch.cuda.stream(stream):
                     while not errors:
                         i = next(nxt)
-                        if i >= len(seeds):
+                        if i >= count:
                             return
-                        out[i] = gp.prove_proof(seed=seeds[i], **kw)
+                        one(gp, i)
             except BaseException as e:  # noqa: BLE001
                 errors.append(e)
-        threads = [threading.Thread(target=work, args=(w,)) for w in range(max(1, min(workers, len(seeds) - 1)))]
+        threads = [threading.Thread(target=work, args=(w,)) for w in range(max(1, min(workers, count - 1)))]
         # A worker that wakes from a stream synchronisation needs the interpreter lock back; with CPython's default
         # 5 ms switch interval it can wait that long for a thread that is busy converting arrays, which is a third
         # of a whole proof.  Ask for the lock every 50 us while the workers run.
@@ -530,8 +656,7 @@ class GpuProver:
             raise errors[0]
         torch.cuda.synchronize(self.dev)
         dt = time.perf_counter() - t0
-        self.timings = {"total": dt, "proofs_per_s": len(seeds) / dt, "workers": len(threads)}
-        return out
+        self.timings = {"total": dt, "proofs_per_s": count / dt, "workers": len(threads)}
 
     def prove_minimal(self, **kw):
         """The proof with ONE decommitment per tree -- queries sorted and deduplicated, only the siblings and fold

@@ -659,11 +659,16 @@ class StwoDeviceBatch(_DeviceBatch):
                  index: Optional[Sequence[int]] = None):
         """`index` (optional): proof i of the batch is records[index[i]].  The distinct records are
         then uploaded once, replicated by a device gather and re-tiled by ss_stwo_pack_dev, so a
-        65 536-proof batch made of a few distinct proofs costs no 11 GB host pack and upload."""
+        65 536-proof batch made of a few distinct proofs costs no 11 GB host pack and upload.
+        `records` may also be an int32 device tensor [n, record_words] (prover.GpuProver.prove_records): the batch is
+        then packed where it lies (Verifier.pack_stwo_records_dev)."""
         L = B.lib()
         self.cfg, self.mode = cfg, mode
         self.cs = stwo_cfg_struct(cfg, mode, ver.stwo_flags)
-        if index is None:
+        if _torch().is_tensor(records):
+            n = int(records.shape[0])
+            packed = ver.pack_stwo_records_dev(cfg, mode, records)
+        elif index is None:
             n = len(records)
             packed = pack_stwo(cfg, mode, records, ver.stwo_flags)
         else:
@@ -1272,13 +1277,20 @@ class Verifier:
     def pack_stwo_on_device(self, cfg: StwoConfig, mode: int, records: Sequence[np.ndarray]):
         """Upload records as they are and re-tile them with ss_stwo_pack_dev; returns the batch
         tensor (int32 view of the u32 words)."""
+        flat = np.ascontiguousarray(np.stack(records), dtype=np.uint32)
+        return self.pack_stwo_records_dev(cfg, mode, _to_dev(flat, self.device))
+
+    def pack_stwo_records_dev(self, cfg: StwoConfig, mode: int, rec_dev):
+        """The same for records that are already resident: `rec_dev` is an int32 device tensor [n, record_words], one
+        record per row (what prover.GpuProver.prove_records returns), re-tiled by ss_stwo_pack_dev with no upload."""
         torch = _torch()
         cs = stwo_cfg_struct(cfg, mode, self.stwo_flags)
-        flat = np.ascontiguousarray(np.stack(records), dtype=np.uint32)
-        rec_dev = _to_dev(flat.reshape(-1), self.device)
-        words = B.lib().ss_stwo_batch_words(C.byref(cs), len(records))
-        out = torch.empty(words, dtype=torch.int32, device=self.device)
-        B.check(B.lib().ss_stwo_pack_dev(self.ctx, C.byref(cs), len(records), rec_dev.data_ptr(),
+        n, want = int(rec_dev.shape[0]), B.lib().ss_stwo_record_words(C.byref(cs))
+        if (rec_dev.dtype != torch.int32 or rec_dev.dim() != 2 or rec_dev.shape[1] != want or not rec_dev.is_contiguous()
+                or not rec_dev.is_cuda):
+            raise ValueError("records must be a contiguous int32 device tensor of shape (n, %d)" % want)
+        out = torch.empty(B.lib().ss_stwo_batch_words(C.byref(cs), n), dtype=torch.int32, device=self.device)
+        B.check(B.lib().ss_stwo_pack_dev(self.ctx, C.byref(cs), n, rec_dev.data_ptr(),
                                          out.data_ptr(), int(torch.cuda.current_stream(self.device).cuda_stream)))
         torch.cuda.synchronize(self.device)
         return out

@@ -1,0 +1,63 @@
+#!/usr/bin/env python3
+"""prove -> record-in-HBM, host route against device route, alternating in one process on one MI355X:
+  host    prove_proof + verifier.stwo_record + upload          | prove_many(workers) + the same conversion
+  device  prove_record (ss_p_finish_dev, ss_p_decommit_record) | prove_records(workers)
+Both end with the record(s) resident and the device synchronised, and must hold the same words.
+`python tools/prover_record_bench.py [trace_log] [reps] [proofs] [workers]`."""
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from stark_symphony_amd import prover, verifier  # noqa: E402
+
+trace_log = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+reps = int(sys.argv[2]) if len(sys.argv) > 2 else 15
+n_many = int(sys.argv[3]) if len(sys.argv) > 3 else 48
+workers = int(sys.argv[4]) if len(sys.argv) > 4 else 4
+kw = dict(n_cols=4, trace_log=trace_log, log_blowup=4, n_queries=16, pow_bits=5, hash="sha256")
+gp = prover.GpuProver(verifier.Verifier(0))
+torch = gp.torch
+
+
+def upload(proofs):
+    rec = torch.from_numpy(np.stack([verifier.stwo_record(p) for p in proofs]).view(np.int32)).to(gp.dev)
+    torch.cuda.synchronize(gp.dev)
+    return rec
+
+
+def timed(fn):
+    torch.cuda.synchronize(gp.dev)
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize(gp.dev)
+    return time.perf_counter() - t0, out
+
+
+routes = {
+    "host_one": lambda: upload([gp.prove_proof(seed=0, **kw)])[0],
+    "device_one": lambda: gp.prove_record(seed=0, **kw),
+    "host_many": lambda: upload(gp.prove_many(range(n_many), workers=workers, **kw)),
+    "device_many": lambda: gp.prove_records(range(n_many), workers=workers, **kw),
+}
+times = {k: [] for k in routes}
+for r in range(reps + 1):  # round 0 warms every route (allocator pools, worker streams, code objects)
+    outs = {}
+    for name, fn in routes.items():
+        if name.endswith("many") and r > (reps + 2) // 3:
+            continue
+        dt, outs[name] = timed(fn)
+        if r:
+            times[name].append(dt / (n_many if name.endswith("many") else 1))
+    assert torch.equal(outs["host_one"], outs["device_one"])
+    assert "host_many" not in outs or torch.equal(outs["host_many"], outs["device_many"])
+result = {k: {"median_ms": 1e3 * statistics.median(v), "min_ms": 1e3 * min(v), "max_ms": 1e3 * max(v), "runs": len(v)}
+          for k, v in times.items()}
+print(json.dumps({"metric": "prove -> resident record, 2^%d x 4, blowup 16, Q=16, per proof" % trace_log,
+                  "proofs_in_many": n_many, "workers": workers, "routes": result}))
