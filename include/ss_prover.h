@@ -30,6 +30,9 @@
 /* The end of a proof without the host: transcript tail (last layer, proof of work, queries) and the decommitment
  * written as the verifier's per-query record in device memory.                                                */
 #include "ss_prover_record.h"
+/* The start of a proof without the host: the transcript up to the FRI commit (cp_alpha, OODS point and samples,
+ * deep_alpha and the DEEP coefficients) with every drawn value kept in device memory.                          */
+#include "ss_prover_transcript.h"
 
 #ifdef __cplusplus
 extern "C" {

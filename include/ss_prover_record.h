@@ -24,6 +24,7 @@ extern "C" {
 /* Bits ss_p_finish_dev ORs into *err_dev (the caller zeroes the word once and reads it when it synchronises). */
 #define SS_P_ERR_LAST_LAYER 1u /* the last FRI layer is not constant: the quotient is not of low degree      */
 #define SS_P_ERR_POW_SPAN 2u   /* no nonce in [0, span): state, nonce and queries are NOT those of the proof */
+#define SS_P_ERR_TRANSCRIPT 4u /* ss_prover_transcript.h: a draw_qm31 ran out of tries, or 1 + t^2 has no inverse */
 
 /* The transcript after the FRI commit, one workgroup: check that the n_last QM31 values of the last layer are
  * all equal (else SS_P_ERR_LAST_LAYER; the steps below run all the same), mix last[0] (channel.simf:31-172), find

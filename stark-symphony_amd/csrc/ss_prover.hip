@@ -607,8 +607,8 @@ __global__ void p_merkle_dup_kernel(size_t n, const uint32_t *__restrict__ leaf,
 }
 
 // ----------------------------------------------------------------------------- composition
-__global__ void p_composition_kernel(uint32_t n_log, uint32_t n_cols, const uint32_t *__restrict__ ev,
-                                     const uint32_t *__restrict__ hx, QM31 alpha, uint32_t *__restrict__ out)
+__device__ __forceinline__ void composition_row(uint32_t n_log, uint32_t n_cols, const uint32_t *__restrict__ ev,
+                                                const uint32_t *__restrict__ hx, QM31 alpha, uint32_t *__restrict__ out)
 {
     const uint32_t size = 1u << (n_log + 1);
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -631,6 +631,18 @@ __global__ void p_composition_kernel(uint32_t n_log, uint32_t n_cols, const uint
     out[(size_t)size + i] = m31_mul(acc.b, van_inv);
     out[(size_t)2 * size + i] = m31_mul(acc.c, van_inv);
     out[(size_t)3 * size + i] = m31_mul(acc.d, van_inv);
+}
+__global__ void p_composition_kernel(uint32_t n_log, uint32_t n_cols, const uint32_t *__restrict__ ev,
+                                     const uint32_t *__restrict__ hx, QM31 alpha, uint32_t *__restrict__ out)
+{
+    composition_row(n_log, n_cols, ev, hx, alpha, out);
+}
+// the same rows with alpha read from device memory (written by ss_p_channel_begin_dev): a uniform load
+__global__ void p_composition_dev_kernel(uint32_t n_log, uint32_t n_cols, const uint32_t *__restrict__ ev,
+                                         const uint32_t *__restrict__ hx, const uint32_t *__restrict__ alpha_dev,
+                                         uint32_t *__restrict__ out)
+{
+    composition_row(n_log, n_cols, ev, hx, ldq(alpha_dev), out);
 }
 
 // -------------------------------------------------------------------------- eval at point
@@ -713,11 +725,11 @@ __device__ __forceinline__ CM31 deep_den_inv(QM31 sx, QM31 sy, uint32_t x, uint3
 // product, reduced once per word); the four DEEP denominators (two sample points x two positions)
 // share ONE M31 inversion.  All operands are canonical field elements, so every re-association gives
 // the bits of the straightforward evaluation (which tools/stwo_prover.py performs).
-__global__ void __launch_bounds__(256)
-p_quotients_kernel(uint32_t lde_log, uint32_t n_cols, const uint32_t *__restrict__ trace_lde,
-                   const uint32_t *__restrict__ cp_lde, uint32_t cp_log, const uint32_t *__restrict__ hx,
-                   const uint32_t *__restrict__ hy, const uint32_t *__restrict__ bcoef, QuotArgs q,
-                   uint32_t *__restrict__ out)
+__device__ __forceinline__ void
+quotients_pair(uint32_t lde_log, uint32_t n_cols, const uint32_t *__restrict__ trace_lde,
+               const uint32_t *__restrict__ cp_lde, uint32_t cp_log, const uint32_t *__restrict__ hx,
+               const uint32_t *__restrict__ hy, const uint32_t *__restrict__ bcoef, const QuotArgs &q,
+               uint32_t *__restrict__ out)
 {
     const size_t size = (size_t)1 << lde_log;
     const size_t h = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -788,6 +800,28 @@ p_quotients_kernel(uint32_t lde_log, uint32_t n_cols, const uint32_t *__restrict
         const QM31 b2 = qm31_mul_cm31(qm31_sub(s2[p], t2), dinv[2 + p]);
         stq(out + 4 * (2 * h + p), qm31_add(qm31_mul(b1, q.alpha16), b2));
     }
+}
+__global__ void __launch_bounds__(256)
+p_quotients_kernel(uint32_t lde_log, uint32_t n_cols, const uint32_t *__restrict__ trace_lde,
+                   const uint32_t *__restrict__ cp_lde, uint32_t cp_log, const uint32_t *__restrict__ hx,
+                   const uint32_t *__restrict__ hy, const uint32_t *__restrict__ bcoef, QuotArgs q,
+                   uint32_t *__restrict__ out)
+{
+    quotients_pair(lde_log, n_cols, trace_lde, cp_lde, cp_log, hx, hy, bcoef, q, out);
+}
+// The same pairs with the nine scalars read from device memory (points: px, py, p2x, p2y as ss_p_oods_point_dev writes
+// them; sums: A1, C1, A2, C2, alpha^16 as ss_p_deep_coeffs_dev does).  The 36 addresses do not depend on the lane, so
+// the loads are uniform and are made once per wavefront; the per-pair arithmetic is that of p_quotients_kernel.
+__global__ void __launch_bounds__(256)
+p_quotients_dev_kernel(uint32_t lde_log, uint32_t n_cols, const uint32_t *__restrict__ trace_lde,
+                       const uint32_t *__restrict__ cp_lde, uint32_t cp_log, const uint32_t *__restrict__ hx,
+                       const uint32_t *__restrict__ hy, const uint32_t *__restrict__ bcoef,
+                       const uint32_t *__restrict__ points, const uint32_t *__restrict__ sums, uint32_t *__restrict__ out)
+{
+    QuotArgs q;
+    q.px = ldq(points); q.py = ldq(points + 4); q.p2x = ldq(points + 8); q.p2y = ldq(points + 12);
+    q.a1 = ldq(sums); q.c1 = ldq(sums + 4); q.a2 = ldq(sums + 8); q.c2 = ldq(sums + 12); q.alpha16 = ldq(sums + 16);
+    quotients_pair(lde_log, n_cols, trace_lde, cp_lde, cp_log, hx, hy, bcoef, q, out);
 }
 
 // ------------------------------------------------------------------------------- fri fold
@@ -1183,6 +1217,18 @@ extern "C" int ss_p_composition(ss_ctx *ctx, uint32_t n_log, uint32_t n_cols, co
     return SS_OK;
 }
 
+extern "C" int ss_p_composition_dev(ss_ctx *ctx, uint32_t n_log, uint32_t n_cols, const uint32_t *ev, const uint32_t *hx_c,
+                                    const uint32_t *alpha_dev, uint32_t *out, void *stream)
+{
+    SS_DEVICE_GUARD(ctx);
+    if (!ev || !hx_c || !alpha_dev || !out || n_log < 1 || n_log > 26)
+        return ss_internal_set_err(SS_ERR_ARG, "ss_p_composition_dev: bad argument");
+    hipLaunchKernelGGL(p_composition_dev_kernel, dim3(blocks_for(1u << (n_log + 1))), dim3(256), 0, (hipStream_t)stream,
+                       n_log, n_cols, ev, hx_c, alpha_dev, out);
+    P_TRY(hipGetLastError());
+    return SS_OK;
+}
+
 // factors: m QM31 values on the HOST (y, x, pi(x), pi^2(x), ...), bit 0 first
 extern "C" int ss_p_eval_at_point(ss_ctx *ctx, uint32_t m, const uint32_t *coeffs, const uint32_t *factors_host,
                                   uint32_t *scratch, uint32_t *out, void *stream)
@@ -1277,6 +1323,21 @@ extern "C" int ss_p_quotients(ss_ctx *ctx, uint32_t lde_log, uint32_t n_cols, co
     const size_t half = (size_t)1 << (lde_log - 1);
     hipLaunchKernelGGL(p_quotients_kernel, dim3(blocks_for(half)), dim3(256), 0, (hipStream_t)stream,
                        lde_log, n_cols, trace_lde, cp_lde, cp_log, hx_hy, hx_hy + half, bcoef, q, out);
+    P_TRY(hipGetLastError());
+    return SS_OK;
+}
+
+extern "C" int ss_p_quotients_dev(ss_ctx *ctx, uint32_t lde_log, uint32_t n_cols, const uint32_t *trace_lde,
+                                  const uint32_t *cp_lde, uint32_t cp_log, const uint32_t *hx_hy, const uint32_t *bcoef,
+                                  const uint32_t *points_dev, const uint32_t *sums_alpha16_dev, uint32_t *out, void *stream)
+{
+    SS_DEVICE_GUARD(ctx);
+    if (!trace_lde || !cp_lde || !hx_hy || !bcoef || !points_dev || !sums_alpha16_dev || !out || lde_log < 2 ||
+        lde_log > 28 || (cp_log != lde_log && cp_log + 1 != lde_log))
+        return ss_internal_set_err(SS_ERR_ARG, "ss_p_quotients_dev: bad argument");
+    const size_t half = (size_t)1 << (lde_log - 1);
+    hipLaunchKernelGGL(p_quotients_dev_kernel, dim3(blocks_for(half)), dim3(256), 0, (hipStream_t)stream,
+                       lde_log, n_cols, trace_lde, cp_lde, cp_log, hx_hy, hx_hy + half, bcoef, points_dev, sums_alpha16_dev, out);
     P_TRY(hipGetLastError());
     return SS_OK;
 }

@@ -12,6 +12,8 @@ tools/stwo_prover.py -- and therefore to the reference's two fixtures
 (tests/test_gpu_prover.py).  `prove_record` / `prove_records` give the same proof as the verifier's
 per-query record (include/ss_verify.h) written by the GPU: after the FRI commit the transcript's tail
 and the decommitment run in two kernels (include/ss_prover_record.h) and only an error word is read.
+With transcript="device" the transcript before the FRI commit runs on the GPU as well
+(include/ss_prover_transcript.h): the whole proof is enqueued without a host read.
 """
 from __future__ import annotations
 
@@ -142,6 +144,15 @@ class GpuProver:
         sig("ss_p_pow", C.c_uint32, u32p, C.c_uint64, C.c_uint64, C.c_uint64, u32p)
         sig("ss_p_finish_dev", C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, u32p, u32p, sz, u32p, u32p, u32p)
         sig("ss_p_decommit_record", C.POINTER(B.StwoCfg), vp, u32p, u32p, u32p, u32p, u32p, u32p, u32p)
+        # include/ss_prover_transcript.h
+        sig("ss_p_channel_begin_dev", C.c_uint32, u32p, u32p, u32p, u32p, u32p)
+        sig("ss_p_composition_dev", C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p)
+        sig("ss_p_oods_point_dev", C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, u32p, u32p)
+        sig("ss_p_eval_at_point_dev", C.c_uint32, C.c_uint32, u32p, sz, u32p, u32p, u32p)
+        sig("ss_p_deep_coeffs_dev", C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, u32p, u32p)
+        sig("ss_p_quotients_dev", C.c_uint32, C.c_uint32, u32p, u32p, C.c_uint32, u32p, u32p, u32p, u32p, u32p)
+        L.ss_p_eval_scratch_words.restype = sz
+        L.ss_p_eval_scratch_words.argtypes = [C.c_uint32, C.c_uint32]
         self._dom: Dict[int, tuple] = {}
         self._workers: list = []  # (prover, stream) of prove_many
         self._pending = None  # (commit, record, error word) of a prove_record not yet checked
@@ -266,15 +277,22 @@ class GpuProver:
 
     # -- the protocol ----------------------------------------------------------------------
     def _commit(self, n_cols: int = 4, trace_log: int = 9, log_blowup: int = 4, n_queries: int = 16,
-                pow_bits: int = 5, seed: int = 0, hash: str = "sha256"):
+                pow_bits: int = 5, seed: int = 0, hash: str = "sha256", transcript: str = "host", err=None):
         """The protocol up to and including the FRI commit, shared by prove_proof and prove_record: everything the rest
-        of a proof is made from, still on the device (trees, layers, samples, the channel state after the last fold)."""
+        of a proof is made from, still on the device (trees, layers, samples, the channel state after the last fold).
+        transcript="device" (prove_record only; `err` = its error word): the channel and the scalar QM31 algebra run in
+        the kernels of include/ss_prover_transcript.h, and nothing here reads from the device or waits for it."""
         import types
         torch = self.torch
+        if transcript not in ("host", "device"):
+            raise ValueError("transcript must be 'host' or 'device'")
+        on_dev = transcript == "device"
         t_start = time.perf_counter()
         marks: List[Tuple[str, float]] = []
 
         def mark(name: str) -> None:
+            if on_dev:  # no synchronisation between phases: timings carries the total only
+                return
             torch.cuda.current_stream(self.dev).synchronize()  # this proof's stream only: others may be in flight (prove_many)
             marks.append((name, time.perf_counter()))
         n, L, N = trace_log, trace_log + log_blowup, n_cols
@@ -293,17 +311,28 @@ class GpuProver:
         trace_tree = self.merkle(hsel, lambda lv: self._call(
             "ss_p_hash_rows", hsel, size_L, N, lde.data_ptr(), size_L, lv.data_ptr()), size_L)
         const_root = H(b"").digest()
-        trace_root = self._root(trace_tree, size_L)
-        mark("trace commit")
-        ch.mix(const_root)
-        ch.mix(trace_root)
-        cp_alpha = ch.draw_qm31()
+        trace_root = cp_root = oods_trace = oods_cp = None
+        if on_dev:
+            # channel[9], cp_alpha[4], points[16], sums + alpha^16 [20], fold factors of P [n][4] and of 2P [n - 1][4]
+            tr = self._empty(52 + 8 * n)
+            state, cp_alpha_dev, points, sums, fac = tr[:9], tr[12:16], tr[16:32], tr[32:52], tr[52:]
+            self._call("ss_p_channel_begin_dev", hsel, (C.c_uint32 * 8)(*np.frombuffer(const_root, dtype=">u4")),
+                       trace_tree[2 * size_L - 2].data_ptr(), state.data_ptr(), cp_alpha_dev.data_ptr(), err.data_ptr())
+        else:
+            trace_root = self._root(trace_tree, size_L)
+            mark("trace commit")
+            ch.mix(const_root)
+            ch.mix(trace_root)
+            cp_alpha = ch.draw_qm31()
 
         # ---- composition polynomial on the coset of log size n + 1, 16 partition columns
         ev = self.extend(coefs, n + 1)
         _, _, hxhy_c = self.domain(n + 1)
         F = self._empty(4, 1 << (n + 1))
-        self._call("ss_p_composition", n, N, ev.data_ptr(), hxhy_c.data_ptr(), self._q(cp_alpha), F.data_ptr())
+        if on_dev:
+            self._call("ss_p_composition_dev", n, N, ev.data_ptr(), hxhy_c.data_ptr(), cp_alpha_dev.data_ptr(), F.data_ptr())
+        else:
+            self._call("ss_p_composition", n, N, ev.data_ptr(), hxhy_c.data_ptr(), self._q(cp_alpha), F.data_ptr())
         self.fft(n + 1, F, True)
         # Partition 4c + part of coordinate c takes the coefficients whose two lowest index bits are `part` and is a
         # polynomial in x alone: in the basis of size n its coefficients sit at the even positions (no y term).  Kept
@@ -322,74 +351,94 @@ class GpuProver:
         self._call("ss_p_hash_rows", hsel, half_L, 16, cp_lde.data_ptr(), half_L, pair_leaf.data_ptr())
         cp_tree = self.merkle(hsel, lambda lv: self._call(
             "ss_p_merkle_dup", hsel, half_L, pair_leaf.data_ptr(), lv.data_ptr()), half_L)
-        cp_root = self._root(cp_tree, half_L)
-        mark("composition commit")
-        ch.mix(cp_root)
-
-        # ---- OODS point, samples
-        t = ch.draw_qm31()
-        t_sq = qmul(t, t)
-        inv = qinv(qadd(ONE, t_sq))
-        px, py = qmul(qsub(ONE, t_sq), inv), qmul(qadd(t, t), inv)
-        p2x = qsub(qadd(qmul(px, px), qmul(px, px)), ONE)
-        p2y = qadd(qmul(px, py), qmul(px, py))
-
-        def factors(x: Q4, y: Q4, m: int) -> np.ndarray:
-            f = [y, x]
-            cur = x
-            for _ in range(2, m):
-                cur = qsub(qadd(qmul(cur, cur), qmul(cur, cur)), ONE)
-                f.append(cur)
-            return np.array(f[:m], dtype=np.uint32).reshape(-1)
-        scratch = self._empty(max(N, 16) * (3 << n))
-        samples = self._empty(N + 16, 4)
-        f1, f2 = factors(px, py, n), factors(p2x, p2y, n)
-        # all columns of a commitment are sampled at one point: one batched fold chain each
-        self._call("ss_p_eval_at_point_batch", n, N, coefs.data_ptr(), 1 << n, f1.ctypes.data, scratch.data_ptr(),
-                   samples.data_ptr())
-        if n > 1:
-            f2x = np.ascontiguousarray(f2[4:])  # no y term: the factors x, pi(x), ... over the compact coefficients
-            self._call("ss_p_eval_at_point_batch", n - 1, 16, cp_coefs.data_ptr(), 1 << (n - 1), f2x.ctypes.data,
-                       scratch.data_ptr(), samples[N:].data_ptr())
-        else:  # a two-row trace: every partition is a constant
-            samples[N:] = 0
-            samples[N:, 0] = cp_coefs[:, 0]
-        samp = self._host(samples).astype(np.int64)
-        oods_trace = [tuple(int(x) for x in samp[k]) for k in range(N)]
-        oods_cp = [tuple(int(x) for x in samp[N + k]) for k in range(16)]
-        ch.mix(b"".join(_be(v) for v in oods_trace) + b"".join(_be(v) for v in oods_cp))
-        deep_alpha = ch.draw_qm31()
-        mark("oods")
-
-        # ---- DEEP quotients (trace batch at P, composition batch at 2P)
-        bco: List[Q4] = []
-        sums: List[Q4] = []
-        for sp_y, vals in ((py, oods_trace), (p2y, oods_cp)):
-            A, Cc, alpha_i = ZERO, ZERO, deep_alpha
-            for v in vals:
-                a, b, c = _interpolant(sp_y, v, alpha_i)
-                bco.append(b)
-                A, Cc = qadd(A, a), qadd(Cc, c)
-                alpha_i = qmul(alpha_i, deep_alpha)
-            sums += [A, Cc]
-        a16 = ONE
-        for _ in range(16):
-            a16 = qmul(a16, deep_alpha)
-        bcoef = torch.from_numpy(np.array(bco, dtype=np.uint32).view(np.int32)).to(self.dev)
-        pts = (C.c_uint32 * 8)(*px, *py)
-        pts2 = (C.c_uint32 * 8)(*p2x, *p2y)
-        sa = (C.c_uint32 * 20)(*[x for v in sums + [a16] for x in v])
         _, itw_L, hxhy_L = self.domain(L)
         layer = self._empty(size_L, 4)
-        self._call("ss_p_quotients", L, N, lde.data_ptr(), cp_lde.data_ptr(), L - 1, hxhy_L.data_ptr(),
-                   bcoef.data_ptr(), pts, pts2, sa, layer.data_ptr())
-        mark("quotients")
+        samples = self._empty(N + 16, 4)
+        if on_dev:
+            # ---- OODS point, samples, DEEP coefficients and quotients: six launches, every scalar stays in `tr`
+            f1, f2x = fac[:4 * n], fac[4 * n:]
+            self._call("ss_p_oods_point_dev", hsel, n, state.data_ptr(), cp_tree[2 * half_L - 2].data_ptr(), points.data_ptr(),
+                       f1.data_ptr(), f2x.data_ptr() if n > 1 else None, err.data_ptr())
+            scratch = self._empty(max(4, self.lib.ss_p_eval_scratch_words(n, max(N, 16))))
+            self._call("ss_p_eval_at_point_dev", n, N, coefs.data_ptr(), 1 << n, f1.data_ptr(), scratch.data_ptr(), samples.data_ptr())
+            if n > 1:
+                self._call("ss_p_eval_at_point_dev", n - 1, 16, cp_coefs.data_ptr(), 1 << (n - 1), f2x.data_ptr(),
+                           scratch.data_ptr(), samples[N:].data_ptr())
+            else:  # a two-row trace: every partition is a constant
+                samples[N:] = 0
+                samples[N:, 0] = cp_coefs[:, 0]
+            bcoef = self._empty(N + 16, 4)
+            self._call("ss_p_deep_coeffs_dev", hsel, N, state.data_ptr(), samples.data_ptr(), points.data_ptr(),
+                       bcoef.data_ptr(), sums.data_ptr(), err.data_ptr())
+            self._call("ss_p_quotients_dev", L, N, lde.data_ptr(), cp_lde.data_ptr(), L - 1, hxhy_L.data_ptr(),
+                       bcoef.data_ptr(), points.data_ptr(), sums.data_ptr(), layer.data_ptr())
+        else:
+            cp_root = self._root(cp_tree, half_L)
+            mark("composition commit")
+            ch.mix(cp_root)
+
+            # ---- OODS point, samples
+            t = ch.draw_qm31()
+            t_sq = qmul(t, t)
+            inv = qinv(qadd(ONE, t_sq))
+            px, py = qmul(qsub(ONE, t_sq), inv), qmul(qadd(t, t), inv)
+            p2x = qsub(qadd(qmul(px, px), qmul(px, px)), ONE)
+            p2y = qadd(qmul(px, py), qmul(px, py))
+
+            def factors(x: Q4, y: Q4, m: int) -> np.ndarray:
+                f = [y, x]
+                cur = x
+                for _ in range(2, m):
+                    cur = qsub(qadd(qmul(cur, cur), qmul(cur, cur)), ONE)
+                    f.append(cur)
+                return np.array(f[:m], dtype=np.uint32).reshape(-1)
+            scratch = self._empty(max(N, 16) * (3 << n))
+            f1, f2 = factors(px, py, n), factors(p2x, p2y, n)
+            # all columns of a commitment are sampled at one point: one batched fold chain each
+            self._call("ss_p_eval_at_point_batch", n, N, coefs.data_ptr(), 1 << n, f1.ctypes.data, scratch.data_ptr(),
+                       samples.data_ptr())
+            if n > 1:
+                f2x = np.ascontiguousarray(f2[4:])  # no y term: the factors x, pi(x), ... over the compact coefficients
+                self._call("ss_p_eval_at_point_batch", n - 1, 16, cp_coefs.data_ptr(), 1 << (n - 1), f2x.ctypes.data,
+                           scratch.data_ptr(), samples[N:].data_ptr())
+            else:  # a two-row trace: every partition is a constant
+                samples[N:] = 0
+                samples[N:, 0] = cp_coefs[:, 0]
+            samp = self._host(samples).astype(np.int64)
+            oods_trace = [tuple(int(x) for x in samp[k]) for k in range(N)]
+            oods_cp = [tuple(int(x) for x in samp[N + k]) for k in range(16)]
+            ch.mix(b"".join(_be(v) for v in oods_trace) + b"".join(_be(v) for v in oods_cp))
+            deep_alpha = ch.draw_qm31()
+            mark("oods")
+
+            # ---- DEEP quotients (trace batch at P, composition batch at 2P)
+            bco: List[Q4] = []
+            sums: List[Q4] = []
+            for sp_y, vals in ((py, oods_trace), (p2y, oods_cp)):
+                A, Cc, alpha_i = ZERO, ZERO, deep_alpha
+                for v in vals:
+                    a, b, c = _interpolant(sp_y, v, alpha_i)
+                    bco.append(b)
+                    A, Cc = qadd(A, a), qadd(Cc, c)
+                    alpha_i = qmul(alpha_i, deep_alpha)
+                sums += [A, Cc]
+            a16 = ONE
+            for _ in range(16):
+                a16 = qmul(a16, deep_alpha)
+            bcoef = torch.from_numpy(np.array(bco, dtype=np.uint32).view(np.int32)).to(self.dev)
+            pts = (C.c_uint32 * 8)(*px, *py)
+            pts2 = (C.c_uint32 * 8)(*p2x, *p2y)
+            sa = (C.c_uint32 * 20)(*[x for v in sums + [a16] for x in v])
+            self._call("ss_p_quotients", L, N, lde.data_ptr(), cp_lde.data_ptr(), L - 1, hxhy_L.data_ptr(),
+                       bcoef.data_ptr(), pts, pts2, sa, layer.data_ptr())
+            mark("quotients")
 
         # ---- FRI commit (fri/commit.simf:70-85), channel included, without a host round trip: per
         # layer the Merkle tree, then one lane mixes the root and draws alpha ON THE DEVICE, then the
         # fold reads alpha from device memory.  One download at the end (roots, channel, last layer).
-        state = torch.from_numpy(np.concatenate([np.frombuffer(ch.digest, dtype=">u4").astype(np.uint32),
-                                                 np.array([ch.counter], dtype=np.uint32)]).view(np.int32)).to(self.dev)
+        if not on_dev:
+            state = torch.from_numpy(np.concatenate([np.frombuffer(ch.digest, dtype=">u4").astype(np.uint32),
+                                                     np.array([ch.counter], dtype=np.uint32)]).view(np.int32)).to(self.dev)
         roots_dev = self._empty(K + 1, 8)
         alphas_dev = self._empty(K + 1, 4)
         layers, trees = [], []
@@ -411,7 +460,7 @@ class GpuProver:
             N=N, n=n, L=L, K=K, Q=n_queries, pow_bits=pow_bits, hash=hash, hsel=hsel, ch=ch, mark=mark, marks=marks,
             t_start=t_start, const_root=const_root, trace_root=trace_root, cp_root=cp_root, oods_trace=oods_trace,
             oods_cp=oods_cp, samples=samples, lde=lde, cp_lde=cp_lde, trace_tree=trace_tree, pair_leaf=pair_leaf,
-            cp_tree=cp_tree, layers=layers, trees=trees, state=state, roots_dev=roots_dev, last=layer)
+            cp_tree=cp_tree, layers=layers, trees=trees, state=state, roots_dev=roots_dev, last=layer, on_dev=on_dev)
 
     def _host_tail(self, c):
         """The end of the transcript on the host: one download (channel, FRI roots, last layer), the last layer's mix,
@@ -518,22 +567,27 @@ class GpuProver:
     def _decommit_record(self, c, queries_dev, nonce_dev, out) -> None:
         # one ss_p_tree (levels, values, leaf) per tree: trace, composition, FRI layers
         desc = [(c.trace_tree, c.lde, None), (c.cp_tree, c.cp_lde, c.pair_leaf)] + list(zip(c.trees, c.layers, [None] * (c.K + 1)))
-        trees_dev = self.torch.tensor([[t.data_ptr() if t is not None else 0 for t in row] for row in desc],
-                                      dtype=self.torch.int64).to(self.dev)
+        trees_dev = self.torch.tensor([[t.data_ptr() if t is not None else 0 for t in row] for row in desc], dtype=self.torch.int64)
+        # (device transcript: from pinned memory, so that the upload does not wait for the stream)
+        trees_dev = trees_dev.pin_memory().to(self.dev, non_blocking=True) if c.on_dev else trees_dev.to(self.dev)
         root = (C.c_uint32 * 8)(*np.frombuffer(c.const_root, dtype=">u4").astype(np.uint32))
         self._call("ss_p_decommit_record", C.byref(c.cs), trees_dev.data_ptr(), c.samples.data_ptr(), c.roots_dev.data_ptr(),
                    c.last.data_ptr(), nonce_dev.data_ptr(), root, queries_dev.data_ptr(), out.data_ptr())
 
-    def prove_record(self, out=None, pow_span: Optional[int] = None, check: bool = True, **kw):
+    def prove_record(self, out=None, pow_span: Optional[int] = None, check: bool = True, transcript: str = "host", **kw):
         """The proof of prove_proof(**kw) as the per-query record of include/ss_verify.h (verifier.stwo_record of it, word
         for word), written by the GPU into `out`: int32[record_words] on the device, e.g. a row of a caller's
         [n, record_words] tensor (allocated here when None; it may be uninitialised).  After the FRI commit nothing returns
         to the host but one error word: ss_p_finish_dev ends the transcript (last layer, proof of work over the first
         `pow_span` nonces -- default 2^min(22, pow_bits + 8), the first pass of prove_proof's search -- and queries),
         ss_p_decommit_record gathers the record.  check=False leaves that word unread: the record is then valid once
-        check() has returned, and the caller runs no other proof on this prover before."""
+        check() has returned, and the caller runs no other proof on this prover before.
+        transcript="device": the transcript before the FRI commit runs on the GPU too (include/ss_prover_transcript.h: the
+        three draws, the OODS point and samples, the DEEP coefficients), so between the first launch and check() nothing
+        is read from the device and nothing waits for it; `timings` then carries `total` only.  The same record."""
         self.check()
-        c = self._commit(**kw)
+        err = self._zeros(1) if transcript == "device" else None
+        c = self._commit(transcript=transcript, err=err, **kw)
         from .verifier import MODE_FIXTURE, stwo_cfg_struct
         c.cs = stwo_cfg_struct(self.config(c.N, c.n, c.L - c.n, c.Q, c.pow_bits, 0, c.hash), MODE_FIXTURE)
         words = self.lib.ss_stwo_record_words(C.byref(c.cs))
@@ -542,7 +596,8 @@ class GpuProver:
         if out.dtype != self.torch.int32 or out.numel() != words or not out.is_contiguous() or out.device != c.state.device:
             raise ValueError("out must be %d contiguous int32 words on the prover's device" % words)
         span = pow_span if pow_span is not None else 1 << min(22, c.pow_bits + 8)
-        err = self._zeros(1)
+        if err is None:
+            err = self._zeros(1)
         tail = self._empty(c.Q + 2)  # queries, nonce hi, lo
         self._call("ss_p_finish_dev", c.hsel, c.L, c.Q, c.cs.pow_target, span, c.state.data_ptr(), c.last.data_ptr(),
                    c.last.shape[0], tail.data_ptr(), tail[c.Q:].data_ptr(), err.data_ptr())
@@ -562,6 +617,8 @@ class GpuProver:
             return
         c, out, err = pending
         bits = int(err.cpu()[0])
+        if bits & 4:  # SS_P_ERR_TRANSCRIPT
+            raise AssertionError("transcript: a draw ran out of tries, or 1 + t^2 has no inverse")
         if bits & 1:
             raise AssertionError("last FRI layer is not constant: the quotient is not low degree")
         if bits & 2:
@@ -569,6 +626,9 @@ class GpuProver:
             tail = self.torch.from_numpy(np.array(queries + [nonce >> 32, nonce & 0xFFFFFFFF], dtype=np.uint32).view(np.int32)).to(self.dev)
             self._decommit_record(c, tail, tail[c.Q:], out)
             self.torch.cuda.current_stream(self.dev).synchronize()
+        if c.on_dev:
+            self.timings = {"total": time.perf_counter() - c.t_start}
+            return
         c.mark("tail")
         prev = c.t_start
         self.timings = {}
@@ -578,7 +638,8 @@ class GpuProver:
         self.timings["total"] = prev - c.t_start
 
     def prove_records(self, seeds: Sequence[int], workers: int = 4, **kw):
-        """prove_record for every seed of `seeds` on the schedule of prove_many (the same worker streams and threads):
+        """prove_record for every seed of `seeds` (keywords, transcript= included, are passed on) on the schedule of
+        prove_many (the same worker streams and threads):
         -> int32[len(seeds), record_words] on the device, row i = the record of seeds[i], every row checked and the
         device synchronised.  ss_stwo_pack_dev / Verifier.pack_stwo_records_dev take the tensor as it is."""
         seeds = list(seeds)

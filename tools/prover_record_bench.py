@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""prove -> record-in-HBM, host route against device route, alternating in one process on one MI355X:
+"""prove -> record-in-HBM, three routes alternating in one process on one MI355X:
   host    prove_proof + verifier.stwo_record + upload          | prove_many(workers) + the same conversion
   device  prove_record (ss_p_finish_dev, ss_p_decommit_record) | prove_records(workers)
-Both end with the record(s) resident and the device synchronised, and must hold the same words.
-`python tools/prover_record_bench.py [trace_log] [reps] [proofs] [workers]`."""
+  devtx   prove_record(transcript="device"): the transcript before the FRI commit on the GPU as well
+          (include/ss_prover_transcript.h)                     | prove_records(workers, transcript="device")
+All end with the record(s) resident and the device synchronised, and must hold the same words.
+`python tools/prover_record_bench.py [trace_log] [reps] [proofs] [workers] [n_cols]` (wide256: 14 15 48 4 256)."""
 import json
 import os
 import statistics
@@ -21,7 +23,8 @@ trace_log = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 15
 n_many = int(sys.argv[3]) if len(sys.argv) > 3 else 48
 workers = int(sys.argv[4]) if len(sys.argv) > 4 else 4
-kw = dict(n_cols=4, trace_log=trace_log, log_blowup=4, n_queries=16, pow_bits=5, hash="sha256")
+n_cols = int(sys.argv[5]) if len(sys.argv) > 5 else 4
+kw = dict(n_cols=n_cols, trace_log=trace_log, log_blowup=4, n_queries=16, pow_bits=5, hash="sha256")
 gp = prover.GpuProver(verifier.Verifier(0))
 torch = gp.torch
 
@@ -43,8 +46,10 @@ def timed(fn):
 routes = {
     "host_one": lambda: upload([gp.prove_proof(seed=0, **kw)])[0],
     "device_one": lambda: gp.prove_record(seed=0, **kw),
+    "devtx_one": lambda: gp.prove_record(seed=0, transcript="device", **kw),
     "host_many": lambda: upload(gp.prove_many(range(n_many), workers=workers, **kw)),
     "device_many": lambda: gp.prove_records(range(n_many), workers=workers, **kw),
+    "devtx_many": lambda: gp.prove_records(range(n_many), workers=workers, transcript="device", **kw),
 }
 times = {k: [] for k in routes}
 for r in range(reps + 1):  # round 0 warms every route (allocator pools, worker streams, code objects)
@@ -55,9 +60,10 @@ for r in range(reps + 1):  # round 0 warms every route (allocator pools, worker 
         dt, outs[name] = timed(fn)
         if r:
             times[name].append(dt / (n_many if name.endswith("many") else 1))
-    assert torch.equal(outs["host_one"], outs["device_one"])
-    assert "host_many" not in outs or torch.equal(outs["host_many"], outs["device_many"])
+    assert torch.equal(outs["host_one"], outs["device_one"]) and torch.equal(outs["host_one"], outs["devtx_one"])
+    assert "host_many" not in outs or (torch.equal(outs["host_many"], outs["device_many"]) and
+                                       torch.equal(outs["host_many"], outs["devtx_many"]))
 result = {k: {"median_ms": 1e3 * statistics.median(v), "min_ms": 1e3 * min(v), "max_ms": 1e3 * max(v), "runs": len(v)}
           for k, v in times.items()}
-print(json.dumps({"metric": "prove -> resident record, 2^%d x 4, blowup 16, Q=16, per proof" % trace_log,
+print(json.dumps({"metric": "prove -> resident record, 2^%d x %d, blowup 16, Q=16, per proof" % (trace_log, n_cols),
                   "proofs_in_many": n_many, "workers": workers, "routes": result}))
