@@ -33,6 +33,9 @@
 /* The start of a proof without the host: the transcript up to the FRI commit (cp_alpha, OODS point and samples,
  * deep_alpha and the DEEP coefficients) with every drawn value kept in device memory.                          */
 #include "ss_prover_transcript.h"
+/* The decommitment as the minimal record (one sorted, deduplicated decommitment per tree), planned and gathered on
+ * the device, and the packing of a batch of such records behind an offset table.                                */
+#include "ss_prover_minimal.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -14,6 +14,8 @@ per-query record (include/ss_verify.h) written by the GPU: after the FRI commit 
 and the decommitment run in two kernels (include/ss_prover_record.h) and only an error word is read.
 With transcript="device" the transcript before the FRI commit runs on the GPU as well
 (include/ss_prover_transcript.h): the whole proof is enqueued without a host read.
+`prove_minimal_record` / `prove_minimal_records` end the same way with the MINIMAL record (one sorted, deduplicated
+decommitment per tree), whose layout the GPU plans from the queries (include/ss_prover_minimal.h).
 """
 from __future__ import annotations
 
@@ -144,6 +146,9 @@ class GpuProver:
         sig("ss_p_pow", C.c_uint32, u32p, C.c_uint64, C.c_uint64, C.c_uint64, u32p)
         sig("ss_p_finish_dev", C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, u32p, u32p, sz, u32p, u32p, u32p)
         sig("ss_p_decommit_record", C.POINTER(B.StwoCfg), vp, u32p, u32p, u32p, u32p, u32p, u32p, u32p)
+        # include/ss_prover_minimal.h
+        sig("ss_p_decommit_minimal", C.POINTER(B.StwoCfg), vp, u32p, u32p, u32p, u32p, u32p, u32p, u32p, u32p)
+        sig("ss_p_minimal_pack_dev", sz, u32p, sz, u32p, u32p, vp)
         # include/ss_prover_transcript.h
         sig("ss_p_channel_begin_dev", C.c_uint32, u32p, u32p, u32p, u32p, u32p)
         sig("ss_p_composition_dev", C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p)
@@ -155,7 +160,8 @@ class GpuProver:
         L.ss_p_eval_scratch_words.argtypes = [C.c_uint32, C.c_uint32]
         self._dom: Dict[int, tuple] = {}
         self._workers: list = []  # (prover, stream) of prove_many
-        self._pending = None  # (commit, record, error word) of a prove_record not yet checked
+        self._pending = None  # (commit, record, error word, size word or None) of a prove_record / prove_minimal_record not yet checked
+        self.record_words = None  # size of the last checked prove_minimal_record's record
         self.timings: Dict[str, float] = {}
 
     # -- small helpers ---------------------------------------------------------------------
@@ -564,15 +570,49 @@ class GpuProver:
         from .formats import StwoConfig
         return StwoConfig(n_cols, trace_log, trace_log + log_blowup, n_queries, trace_log - 1, pow_bits, hash)
 
-    def _decommit_record(self, c, queries_dev, nonce_dev, out) -> None:
+    def _decommit_record(self, c, queries_dev, nonce_dev, out, words_out=None) -> None:
+        """ss_p_decommit_record into `out`; with `words_out` (the size word) ss_p_decommit_minimal."""
         # one ss_p_tree (levels, values, leaf) per tree: trace, composition, FRI layers
         desc = [(c.trace_tree, c.lde, None), (c.cp_tree, c.cp_lde, c.pair_leaf)] + list(zip(c.trees, c.layers, [None] * (c.K + 1)))
         trees_dev = self.torch.tensor([[t.data_ptr() if t is not None else 0 for t in row] for row in desc], dtype=self.torch.int64)
         # (device transcript: from pinned memory, so that the upload does not wait for the stream)
         trees_dev = trees_dev.pin_memory().to(self.dev, non_blocking=True) if c.on_dev else trees_dev.to(self.dev)
         root = (C.c_uint32 * 8)(*np.frombuffer(c.const_root, dtype=">u4").astype(np.uint32))
-        self._call("ss_p_decommit_record", C.byref(c.cs), trees_dev.data_ptr(), c.samples.data_ptr(), c.roots_dev.data_ptr(),
-                   c.last.data_ptr(), nonce_dev.data_ptr(), root, queries_dev.data_ptr(), out.data_ptr())
+        args = (C.byref(c.cs), trees_dev.data_ptr(), c.samples.data_ptr(), c.roots_dev.data_ptr(), c.last.data_ptr(),
+                nonce_dev.data_ptr(), root, queries_dev.data_ptr(), out.data_ptr())
+        if words_out is None:
+            self._call("ss_p_decommit_record", *args)
+        else:
+            self._call("ss_p_decommit_minimal", *args, words_out.data_ptr())
+
+    def _enqueue_record(self, minimal: bool, out, words_out, pow_span: Optional[int], transcript: str, kw):
+        """What prove_record and prove_minimal_record share: the protocol up to the FRI commit, ss_p_finish_dev, the
+        decommitment into `out` (one record, or with `minimal` a row of ss_stwo_minimal_max_words words and the size
+        word `words_out`), all enqueued and left pending for check()."""
+        self.check()
+        err = self._zeros(1) if transcript == "device" else None
+        c = self._commit(transcript=transcript, err=err, **kw)
+        from .verifier import MODE_FIXTURE, stwo_cfg_struct
+        c.cs = stwo_cfg_struct(self.config(c.N, c.n, c.L - c.n, c.Q, c.pow_bits, 0, c.hash), MODE_FIXTURE)
+        words = (self.lib.ss_stwo_minimal_max_words if minimal else self.lib.ss_stwo_record_words)(C.byref(c.cs))
+        if out is None:
+            out = self._empty(words)
+        if out.dtype != self.torch.int32 or out.numel() != words or not out.is_contiguous() or out.device != c.state.device:
+            raise ValueError("out must be %d contiguous int32 words on the prover's device" % words)
+        if minimal:
+            if words_out is None:
+                words_out = self._empty(1)
+            if words_out.dtype != self.torch.int32 or words_out.numel() != 1 or words_out.device != c.state.device:
+                raise ValueError("words_out must be one int32 word on the prover's device")
+        span = pow_span if pow_span is not None else 1 << min(22, c.pow_bits + 8)
+        if err is None:
+            err = self._zeros(1)
+        tail = self._empty(c.Q + 2)  # queries, nonce hi, lo
+        self._call("ss_p_finish_dev", c.hsel, c.L, c.Q, c.cs.pow_target, span, c.state.data_ptr(), c.last.data_ptr(),
+                   c.last.shape[0], tail.data_ptr(), tail[c.Q:].data_ptr(), err.data_ptr())
+        self._decommit_record(c, tail, tail[c.Q:], out, words_out)
+        self._pending = (c, out, err, words_out)
+        return out
 
     def prove_record(self, out=None, pow_span: Optional[int] = None, check: bool = True, transcript: str = "host", **kw):
         """The proof of prove_proof(**kw) as the per-query record of include/ss_verify.h (verifier.stwo_record of it, word
@@ -585,38 +625,40 @@ class GpuProver:
         transcript="device": the transcript before the FRI commit runs on the GPU too (include/ss_prover_transcript.h: the
         three draws, the OODS point and samples, the DEEP coefficients), so between the first launch and check() nothing
         is read from the device and nothing waits for it; `timings` then carries `total` only.  The same record."""
-        self.check()
-        err = self._zeros(1) if transcript == "device" else None
-        c = self._commit(transcript=transcript, err=err, **kw)
-        from .verifier import MODE_FIXTURE, stwo_cfg_struct
-        c.cs = stwo_cfg_struct(self.config(c.N, c.n, c.L - c.n, c.Q, c.pow_bits, 0, c.hash), MODE_FIXTURE)
-        words = self.lib.ss_stwo_record_words(C.byref(c.cs))
-        if out is None:
-            out = self._empty(words)
-        if out.dtype != self.torch.int32 or out.numel() != words or not out.is_contiguous() or out.device != c.state.device:
-            raise ValueError("out must be %d contiguous int32 words on the prover's device" % words)
-        span = pow_span if pow_span is not None else 1 << min(22, c.pow_bits + 8)
-        if err is None:
-            err = self._zeros(1)
-        tail = self._empty(c.Q + 2)  # queries, nonce hi, lo
-        self._call("ss_p_finish_dev", c.hsel, c.L, c.Q, c.cs.pow_target, span, c.state.data_ptr(), c.last.data_ptr(),
-                   c.last.shape[0], tail.data_ptr(), tail[c.Q:].data_ptr(), err.data_ptr())
-        self._decommit_record(c, tail, tail[c.Q:], out)
-        self._pending = (c, out, err)
+        out = self._enqueue_record(False, out, None, pow_span, transcript, kw)
         if check:
             self.check()
         return out
 
+    def prove_minimal_record(self, out=None, words_out=None, pow_span: Optional[int] = None, check: bool = True,
+                             transcript: str = "host", **kw):
+        """The proof of prove_proof(**kw) as the MINIMAL record of include/ss_verify_forms.h (verifier.stwo_minimal_record
+        of formats.stwo_minimise of it, word for word), planned and gathered by the GPU (ss_p_decommit_minimal) behind the
+        same _commit and ss_p_finish_dev as prove_record, with the same arguments.  A minimal record's size depends on the
+        queries: `out` is a row of ss_stwo_minimal_max_words words (int32 on the device, allocated here when None, it may
+        be uninitialised) of which the record fills the first `words`, and words_out (one int32 word on the device, e.g.
+        an element of a caller's [n] tensor) receives that size; nothing behind the record is written.  check=True reads
+        the size together with the error word -- still one synchronisation -- and returns out[:words]; check=False returns
+        the whole row, and words_out (and `record_words`) are valid once check() has returned."""
+        out = self._enqueue_record(True, out, words_out, pow_span, transcript, kw)
+        if check:
+            self.check()
+            return out[:self.record_words]
+        return out
+
     def check(self) -> None:
-        """Waits for the last prove_record of this prover (on the current stream) and reads its error word -- the only
-        host read after the FRI commit.  SS_P_ERR_LAST_LAYER raises what prove_proof raises.  SS_P_ERR_POW_SPAN (no
-        nonce in the span) redoes the tail on the host path of prove_proof and the decommitment with the queries and
-        nonce uploaded: the same record."""
+        """Waits for the last prove_record / prove_minimal_record of this prover (on the current stream) and reads its
+        error word (and a minimal record's size with it, into `record_words`) -- the only host read after the FRI commit.
+        SS_P_ERR_LAST_LAYER raises what prove_proof raises.  SS_P_ERR_POW_SPAN (no nonce in the span) redoes the tail on
+        the host path of prove_proof and the decommitment with the queries and nonce uploaded: the same record."""
         pending, self._pending = self._pending, None
         if pending is None:
             return
-        c, out, err = pending
-        bits = int(err.cpu()[0])
+        c, out, err, words = pending
+        if words is None:
+            bits = int(err.cpu()[0])
+        else:
+            bits, self.record_words = (int(x) for x in self.torch.cat([err, words.reshape(1)]).cpu())
         if bits & 4:  # SS_P_ERR_TRANSCRIPT
             raise AssertionError("transcript: a draw ran out of tries, or 1 + t^2 has no inverse")
         if bits & 1:
@@ -624,8 +666,10 @@ class GpuProver:
         if bits & 2:
             _, _, nonce, queries = self._host_tail(c)
             tail = self.torch.from_numpy(np.array(queries + [nonce >> 32, nonce & 0xFFFFFFFF], dtype=np.uint32).view(np.int32)).to(self.dev)
-            self._decommit_record(c, tail, tail[c.Q:], out)
+            self._decommit_record(c, tail, tail[c.Q:], out, words)
             self.torch.cuda.current_stream(self.dev).synchronize()
+            if words is not None:  # (other queries: another size)
+                self.record_words = int(words.cpu().reshape(1)[0])
         if c.on_dev:
             self.timings = {"total": time.perf_counter() - c.t_start}
             return
@@ -654,6 +698,35 @@ class GpuProver:
             gp.prove_record(out=rows[i], seed=seeds[i], **kw)
         self._run_many(len(seeds), workers, one, t0)
         return rows
+
+    def prove_minimal_records(self, seeds: Sequence[int], workers: int = 4, **kw):
+        """prove_minimal_record for every seed of `seeds` on the schedule of prove_records, then packed on the device
+        (ss_p_minimal_pack_dev): every proof writes a row of an [n, max_words] tensor and a word of an [n] size tensor, a
+        scan of the sizes gives the offsets and a copy lays the records back to back.
+        -> (records, offs): int32[offs[n]] and int64[n + 1] on the device, record i = records[offs[i]:offs[i + 1]], every
+        proof checked and the device synchronised.  verifier.StwoMinimalDeviceBatch takes the pair as it is."""
+        torch = self.torch
+        seeds = list(seeds)
+        n = len(seeds)
+        if not n:
+            return self._empty(0), torch.zeros(1, dtype=torch.int64, device=self.dev)
+        t0 = time.perf_counter()
+        words = self._empty(n)
+        first = self.prove_minimal_record(words_out=words[0:1], check=False, seed=seeds[0], **kw)  # also fills the twiddle cache
+        self.check()
+        rows = self._empty(n, first.numel())
+        rows[0] = first
+
+        def one(gp, i):
+            gp.prove_minimal_record(out=rows[i], words_out=words[i:i + 1], seed=seeds[i], **kw)
+        self._run_many(n, workers, one, t0)
+        packed = self._empty(rows.numel())
+        offs = torch.empty(n + 1, dtype=torch.int64, device=self.dev)
+        self._call("ss_p_minimal_pack_dev", n, rows.data_ptr(), rows.shape[1], words.data_ptr(), packed.data_ptr(), offs.data_ptr())
+        total = int(offs[n].cpu())  # the final synchronisation
+        dt = time.perf_counter() - t0
+        self.timings.update(total=dt, proofs_per_s=n / dt)
+        return packed[:total], offs
 
     def prove_many(self, seeds: Sequence[int], workers: int = 4, **kw) -> list:
         """Proofs of the same configuration for every seed of `seeds`, `workers` of them in flight, each on its own

@@ -708,7 +708,9 @@ class StwoDeviceBatch(_DeviceBatch):
 
 class StwoMinimalDeviceBatch(_DeviceBatch):
     """Minimal records resident in HBM (back to back + their offset table) with the scratch batch / workspace the
-    verification fills: ss_stwo_verify_minimal_dev.  `index`: proof i is records[index[i]] (replicated on the device)."""
+    verification fills: ss_stwo_verify_minimal_dev.  `index`: proof i is records[index[i]] (replicated on the device).
+    `records` may also be a pair (flat, offs) of device tensors that is already that form -- int32 words and the int64
+    [n + 1] offset table, as prover.GpuProver.prove_minimal_records returns them: the batch then verifies them where they lie."""
 
     def __init__(self, ver: "Verifier", cfg: StwoConfig, mode: int, records: Sequence[np.ndarray],
                  index: Optional[Sequence[int]] = None):
@@ -716,6 +718,17 @@ class StwoMinimalDeviceBatch(_DeviceBatch):
         L = B.lib()
         self.cfg, self.mode = cfg, mode
         self.cs = stwo_cfg_struct(cfg, mode, ver.stwo_flags)
+        if isinstance(records, tuple) and len(records) == 2 and torch.is_tensor(records[0]):
+            flat, offs = records
+            if (index is not None or flat.dtype != torch.int32 or offs.dtype != torch.int64 or offs.dim() != 1 or offs.numel() < 1
+                    or not flat.is_contiguous() or not offs.is_contiguous() or flat.device != ver.device
+                    or offs.device != ver.device):
+                raise ValueError("resident minimal records are (int32 words, int64 offsets[n + 1]) on the verifier's device, without index")
+            n = offs.numel() - 1
+            self.records, self.offs, self.record_bytes = flat, offs, flat.numel() * 4
+            packed = torch.empty(L.ss_stwo_minimal_batch_words(C.byref(self.cs), n), dtype=torch.int32, device=ver.device)
+            super().__init__(ver, n, packed, L.ss_stwo_minimal_workspace_bytes(C.byref(self.cs), n))
+            return
         order = list(range(len(records))) if index is None else [int(i) for i in index]
         n = len(order)
         sizes = np.array([records[i].size for i in order], dtype=np.uint64)

@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
-"""prove -> record-in-HBM, three routes alternating in one process on one MI355X:
+"""prove -> record-in-HBM, five routes alternating in one process on one MI355X:
   host    prove_proof + verifier.stwo_record + upload          | prove_many(workers) + the same conversion
   device  prove_record (ss_p_finish_dev, ss_p_decommit_record) | prove_records(workers)
   devtx   prove_record(transcript="device"): the transcript before the FRI commit on the GPU as well
           (include/ss_prover_transcript.h)                     | prove_records(workers, transcript="device")
-All end with the record(s) resident and the device synchronised, and must hold the same words.
+  minimal prove_minimal_record (ss_p_decommit_minimal): the MINIMAL record, planned and gathered on the device
+                                                               | prove_minimal_records(workers): + ss_p_minimal_pack_dev
+  minhost the minimal record without that kernel: prove_record, download, verifier.stwo_minimise_record, upload
+          (the queries it needs are taken as known: replayed before the clock starts)   | prove_records + the same
+All end with the record(s) resident and the device synchronised; host / device / devtx must hold the same words, and so
+must minimal / minhost.
 `python tools/prover_record_bench.py [trace_log] [reps] [proofs] [workers] [n_cols]` (wide256: 14 15 48 4 256)."""
 import json
 import os
@@ -35,6 +40,22 @@ def upload(proofs):
     return rec
 
 
+cfg = gp.config(**kw)
+queries = []  # of seed i, for the minhost route
+for seed in range(n_many):
+    gp.prove_proof(seed=seed, **kw)
+    queries.append(list(gp.queries))
+
+
+def minimise_upload(rows):
+    host = rows.cpu().numpy().view(np.uint32)
+    mins = [verifier.stwo_minimise_record(cfg, host[i], queries[i]) for i in range(host.shape[0])]
+    offs = torch.from_numpy(np.concatenate([[0], np.cumsum([m.size for m in mins])]).astype(np.int64)).to(gp.dev)
+    flat = torch.from_numpy(np.concatenate(mins).view(np.int32)).to(gp.dev)
+    torch.cuda.synchronize(gp.dev)
+    return flat, offs
+
+
 def timed(fn):
     torch.cuda.synchronize(gp.dev)
     t0 = time.perf_counter()
@@ -47,9 +68,13 @@ routes = {
     "host_one": lambda: upload([gp.prove_proof(seed=0, **kw)])[0],
     "device_one": lambda: gp.prove_record(seed=0, **kw),
     "devtx_one": lambda: gp.prove_record(seed=0, transcript="device", **kw),
+    "minimal_one": lambda: gp.prove_minimal_record(seed=0, **kw),
+    "minhost_one": lambda: minimise_upload(gp.prove_record(seed=0, **kw)[None])[0],
     "host_many": lambda: upload(gp.prove_many(range(n_many), workers=workers, **kw)),
     "device_many": lambda: gp.prove_records(range(n_many), workers=workers, **kw),
     "devtx_many": lambda: gp.prove_records(range(n_many), workers=workers, transcript="device", **kw),
+    "minimal_many": lambda: gp.prove_minimal_records(range(n_many), workers=workers, **kw),
+    "minhost_many": lambda: minimise_upload(gp.prove_records(range(n_many), workers=workers, **kw)),
 }
 times = {k: [] for k in routes}
 for r in range(reps + 1):  # round 0 warms every route (allocator pools, worker streams, code objects)
@@ -63,7 +88,10 @@ for r in range(reps + 1):  # round 0 warms every route (allocator pools, worker 
     assert torch.equal(outs["host_one"], outs["device_one"]) and torch.equal(outs["host_one"], outs["devtx_one"])
     assert "host_many" not in outs or (torch.equal(outs["host_many"], outs["device_many"]) and
                                        torch.equal(outs["host_many"], outs["devtx_many"]))
+    assert torch.equal(outs["minimal_one"], outs["minhost_one"])
+    assert "minimal_many" not in outs or all(torch.equal(a, b) for a, b in zip(outs["minimal_many"], outs["minhost_many"]))
 result = {k: {"median_ms": 1e3 * statistics.median(v), "min_ms": 1e3 * min(v), "max_ms": 1e3 * max(v), "runs": len(v)}
           for k, v in times.items()}
 print(json.dumps({"metric": "prove -> resident record, 2^%d x %d, blowup 16, Q=16, per proof" % (trace_log, n_cols),
+                  "record_words": outs["device_one"].numel(), "minimal_words_seed0": outs["minimal_one"].numel(),
                   "proofs_in_many": n_many, "workers": workers, "routes": result}))
