@@ -36,6 +36,8 @@
 /* The decommitment as the minimal record (one sorted, deduplicated decommitment per tree), planned and gathered on
  * the device, and the packing of a batch of such records behind an offset table.                                */
 #include "ss_prover_minimal.h"
+/* The FRI commit of every layer that fits in one workgroup (leaves, tree, channel, fold), in one launch.          */
+#include "ss_prover_fri.h"
 
 #ifdef __cplusplus
 extern "C" {

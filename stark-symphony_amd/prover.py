@@ -156,6 +156,12 @@ class GpuProver:
         sig("ss_p_eval_at_point_dev", C.c_uint32, C.c_uint32, u32p, sz, u32p, u32p, u32p)
         sig("ss_p_deep_coeffs_dev", C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, u32p, u32p)
         sig("ss_p_quotients_dev", C.c_uint32, C.c_uint32, u32p, u32p, C.c_uint32, u32p, u32p, u32p, u32p, u32p)
+        # include/ss_prover_fri.h
+        sig("ss_p_fri_tail_dev", C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, u32p, u32p)
+        L.ss_p_fri_tail_log.restype = C.c_uint32
+        L.ss_p_fri_tail_log.argtypes = []
+        L.ss_p_fri_tail_words.restype = sz
+        L.ss_p_fri_tail_words.argtypes = [C.c_uint32, C.c_uint32]
         L.ss_p_eval_scratch_words.restype = sz
         L.ss_p_eval_scratch_words.argtypes = [C.c_uint32, C.c_uint32]
         self._dom: Dict[int, tuple] = {}
@@ -283,11 +289,15 @@ class GpuProver:
 
     # -- the protocol ----------------------------------------------------------------------
     def _commit(self, n_cols: int = 4, trace_log: int = 9, log_blowup: int = 4, n_queries: int = 16,
-                pow_bits: int = 5, seed: int = 0, hash: str = "sha256", transcript: str = "host", err=None):
+                pow_bits: int = 5, seed: int = 0, hash: str = "sha256", transcript: str = "host", err=None,
+                fri_tail: bool = False):
         """The protocol up to and including the FRI commit, shared by prove_proof and prove_record: everything the rest
         of a proof is made from, still on the device (trees, layers, samples, the channel state after the last fold).
         transcript="device" (prove_record only; `err` = its error word): the channel and the scalar QM31 algebra run in
-        the kernels of include/ss_prover_transcript.h, and nothing here reads from the device or waits for it."""
+        the kernels of include/ss_prover_transcript.h, and nothing here reads from the device or waits for it.
+        fri_tail: from the first FRI layer of at most 2^ss_p_fri_tail_log() values on, that layer and every one after it
+        are committed by ONE launch of one workgroup (include/ss_prover_fri.h) in place of four to six launches per layer;
+        their trees and folds are then views of one arena.  The same bits either way."""
         import types
         torch = self.torch
         if transcript not in ("host", "device"):
@@ -448,8 +458,21 @@ class GpuProver:
         roots_dev = self._empty(K + 1, 8)
         alphas_dev = self._empty(K + 1, 4)
         layers, trees = [], []
+        tail_log = self.lib.ss_p_fri_tail_log() if fri_tail else 0
         for l in range(K + 1):
             size = size_L >> l
+            if L - l <= tail_log:
+                # layers l .. K in one launch; block j of the arena = tree [2 n_j][8] then fold [n_j / 2][4], n_j = size >> j
+                off = size_L - (size_L >> l)
+                arena = self._empty(self.lib.ss_p_fri_tail_words(L - l, K + 1 - l))
+                self._call("ss_p_fri_tail_dev", hsel, L - l, K + 1 - l, state.data_ptr(), layer.data_ptr(), itw_L[off:].data_ptr(),
+                           arena.data_ptr(), roots_dev[l:].data_ptr(), alphas_dev[l:].data_ptr())
+                for j in range(K + 1 - l):
+                    n_j, at = size >> j, 36 * (size - (size >> j))
+                    layers.append(layer)
+                    trees.append(arena[at:at + 16 * n_j].view(2 * n_j, 8))
+                    layer = arena[at + 16 * n_j:at + 18 * n_j].view(n_j >> 1, 4)
+                break
             layers.append(layer)
             cur = layer
             tree = self.merkle(hsel, lambda lv: self._call(
@@ -509,9 +532,9 @@ class GpuProver:
         return roots, last, nonce, queries[:c.Q]
 
     def prove_proof(self, n_cols: int = 4, trace_log: int = 9, log_blowup: int = 4, n_queries: int = 16,
-                    pow_bits: int = 5, seed: int = 0, hash: str = "sha256"):
-        """-> formats.StwoProof (arrays; what the verifier's record is made from)."""
-        c = self._commit(n_cols, trace_log, log_blowup, n_queries, pow_bits, seed, hash)
+                    pow_bits: int = 5, seed: int = 0, hash: str = "sha256", fri_tail: bool = False):
+        """-> formats.StwoProof (arrays; what the verifier's record is made from).  fri_tail: see _commit."""
+        c = self._commit(n_cols, trace_log, log_blowup, n_queries, pow_bits, seed, hash, fri_tail=fri_tail)
         N, n, L, K = c.N, c.n, c.L, c.K
         size_L, half_L = 1 << L, 1 << (L - 1)
         lde, cp_lde, trace_tree, pair_leaf, cp_tree, layers, trees = (c.lde, c.cp_lde, c.trace_tree, c.pair_leaf,
@@ -624,7 +647,9 @@ class GpuProver:
         check() has returned, and the caller runs no other proof on this prover before.
         transcript="device": the transcript before the FRI commit runs on the GPU too (include/ss_prover_transcript.h: the
         three draws, the OODS point and samples, the DEEP coefficients), so between the first launch and check() nothing
-        is read from the device and nothing waits for it; `timings` then carries `total` only.  The same record."""
+        is read from the device and nothing waits for it; `timings` then carries `total` only.  The same record.
+        fri_tail=True (any entry of this class takes it): the FRI layers that fit in one workgroup are committed by one
+        launch (include/ss_prover_fri.h) instead of four to six launches each.  The same record again."""
         out = self._enqueue_record(False, out, None, pow_span, transcript, kw)
         if check:
             self.check()
@@ -802,12 +827,12 @@ class GpuProver:
         return stwo_minimise(proof, self.queries)
 
     def prove(self, n_cols: int = 4, trace_log: int = 9, log_blowup: int = 4, n_queries: int = 16,
-              pow_bits: int = 5, seed: int = 0, hash: str = "sha256") -> dict:
+              pow_bits: int = 5, seed: int = 0, hash: str = "sha256", fri_tail: bool = False) -> dict:
         """The same proof in the reference's `proof.json` schema (format C): `prove_proof` plus the
         conversion of 170 KB of hashes into JSON's lists of byte values (3-4 ms of pure Python at the
         2^20 shape, reported as timings["json"])."""
         from .formats import stwo_to_json
-        proof = self.prove_proof(n_cols, trace_log, log_blowup, n_queries, pow_bits, seed, hash)
+        proof = self.prove_proof(n_cols, trace_log, log_blowup, n_queries, pow_bits, seed, hash, fri_tail)
         t0 = time.perf_counter()
         out = stwo_to_json(proof)
         self.timings["json"] = time.perf_counter() - t0

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
-"""prove -> record-in-HBM, five routes alternating in one process on one MI355X:
+"""prove -> record-in-HBM, six routes alternating in one process on one MI355X:
   host    prove_proof + verifier.stwo_record + upload          | prove_many(workers) + the same conversion
   device  prove_record (ss_p_finish_dev, ss_p_decommit_record) | prove_records(workers)
   devtx   prove_record(transcript="device"): the transcript before the FRI commit on the GPU as well
           (include/ss_prover_transcript.h)                     | prove_records(workers, transcript="device")
+  fritail devtx with fri_tail=True: the FRI layers that fit in one workgroup committed by one launch
+          (include/ss_prover_fri.h)                            | prove_records(workers, transcript="device", fri_tail=True)
   minimal prove_minimal_record (ss_p_decommit_minimal): the MINIMAL record, planned and gathered on the device
                                                                | prove_minimal_records(workers): + ss_p_minimal_pack_dev
   minhost the minimal record without that kernel: prove_record, download, verifier.stwo_minimise_record, upload
           (the queries it needs are taken as known: replayed before the clock starts)   | prove_records + the same
-All end with the record(s) resident and the device synchronised; host / device / devtx must hold the same words, and so
+All end with the record(s) resident and the device synchronised; host / device / devtx / fritail must hold the same words, and so
 must minimal / minhost.
 `python tools/prover_record_bench.py [trace_log] [reps] [proofs] [workers] [n_cols]` (wide256: 14 15 48 4 256)."""
 import json
@@ -68,11 +70,13 @@ routes = {
     "host_one": lambda: upload([gp.prove_proof(seed=0, **kw)])[0],
     "device_one": lambda: gp.prove_record(seed=0, **kw),
     "devtx_one": lambda: gp.prove_record(seed=0, transcript="device", **kw),
+    "fritail_one": lambda: gp.prove_record(seed=0, transcript="device", fri_tail=True, **kw),
     "minimal_one": lambda: gp.prove_minimal_record(seed=0, **kw),
     "minhost_one": lambda: minimise_upload(gp.prove_record(seed=0, **kw)[None])[0],
     "host_many": lambda: upload(gp.prove_many(range(n_many), workers=workers, **kw)),
     "device_many": lambda: gp.prove_records(range(n_many), workers=workers, **kw),
     "devtx_many": lambda: gp.prove_records(range(n_many), workers=workers, transcript="device", **kw),
+    "fritail_many": lambda: gp.prove_records(range(n_many), workers=workers, transcript="device", fri_tail=True, **kw),
     "minimal_many": lambda: gp.prove_minimal_records(range(n_many), workers=workers, **kw),
     "minhost_many": lambda: minimise_upload(gp.prove_records(range(n_many), workers=workers, **kw)),
 }
@@ -86,6 +90,8 @@ for r in range(reps + 1):  # round 0 warms every route (allocator pools, worker 
         if r:
             times[name].append(dt / (n_many if name.endswith("many") else 1))
     assert torch.equal(outs["host_one"], outs["device_one"]) and torch.equal(outs["host_one"], outs["devtx_one"])
+    assert torch.equal(outs["host_one"], outs["fritail_one"])
+    assert "host_many" not in outs or torch.equal(outs["host_many"], outs["fritail_many"])
     assert "host_many" not in outs or (torch.equal(outs["host_many"], outs["device_many"]) and
                                        torch.equal(outs["host_many"], outs["devtx_many"]))
     assert torch.equal(outs["minimal_one"], outs["minhost_one"])
