@@ -38,6 +38,8 @@
 #include "ss_prover_minimal.h"
 /* The FRI commit of every layer that fits in one workgroup (leaves, tree, channel, fold), in one launch.          */
 #include "ss_prover_fri.h"
+/* The end of the transcript with the proof of work ground by a grid of workgroups, in one launch.                  */
+#include "ss_prover_pow.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -83,7 +83,7 @@ def prove(args) -> int:
             gp = stwo_prover.GpuProver(ver)
             proof = gp.prove_proof(n_cols=args.n_cols, trace_log=args.trace_log, log_blowup=args.log_blowup,
                                    n_queries=args.n_queries, pow_bits=args.pow_bits, seed=args.seed or 0, hash=args.hash,
-                                   fri_tail=args.fri_tail)
+                                   fri_tail=args.fri_tail, grid_pow=args.grid_pow)
             out = {"json": lambda: json.dumps(formats.stwo_to_json(proof)), "wit": lambda: formats.stwo_to_wit(proof),
                    "simf": lambda: formats.stwo_to_simf(proof),
                    "json-minimal": lambda: json.dumps(formats.stwo_minimal_to_json(formats.stwo_minimise(proof, gp.queries)))}[args.to]()
@@ -140,6 +140,8 @@ def main(argv=None) -> int:
     g.add_argument("--hash", choices=["sha256", "blake2s"], default="sha256")
     g.add_argument("--fri-tail", action="store_true", help="stwo: commit the FRI layers that fit in one workgroup in one "
                                                            "launch (include/ss_prover_fri.h); the same proof")
+    g.add_argument("--grid-pow", action="store_true", help="stwo: grind the proof of work on the whole GPU in one launch "
+                                                           "(include/ss_prover_pow.h); the same proof, for real --pow-bits")
     g.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
     if args.cmd == "convert":

@@ -162,9 +162,12 @@ class GpuProver:
         L.ss_p_fri_tail_log.argtypes = []
         L.ss_p_fri_tail_words.restype = sz
         L.ss_p_fri_tail_words.argtypes = [C.c_uint32, C.c_uint32]
+        # include/ss_prover_pow.h
+        sig("ss_p_finish_grid_dev", C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, u32p, u32p, sz, u32p, u32p, u32p, vp)
         L.ss_p_eval_scratch_words.restype = sz
         L.ss_p_eval_scratch_words.argtypes = [C.c_uint32, C.c_uint32]
         self._dom: Dict[int, tuple] = {}
+        self._pow_work: Dict[int, object] = {}  # stream -> the three work words of ss_p_finish_grid_dev (zero between launches)
         self._workers: list = []  # (prover, stream) of prove_many
         self._pending = None  # (commit, record, error word, size word or None) of a prove_record / prove_minimal_record not yet checked
         self.record_words = None  # size of the last checked prove_minimal_record's record
@@ -491,14 +494,43 @@ class GpuProver:
             oods_cp=oods_cp, samples=samples, lde=lde, cp_lde=cp_lde, trace_tree=trace_tree, pair_leaf=pair_leaf,
             cp_tree=cp_tree, layers=layers, trees=trees, state=state, roots_dev=roots_dev, last=layer, on_dev=on_dev)
 
-    def _host_tail(self, c):
+    def _finish(self, c, target: int, span: int, tail, err, grid_pow: bool) -> None:
+        """ss_p_finish_dev on the commit `c` (tail = queries, nonce hi, lo); grid_pow: ss_p_finish_grid_dev, the same
+        words with the nonce searched by the whole device.  Its three work words are zeroed once per stream, here, and
+        left zero by every launch, so proofs in flight on different streams never share them."""
+        args = (c.hsel, c.L, c.Q, target, min(span, (1 << 64) - 1), c.state.data_ptr(), c.last.data_ptr(), c.last.shape[0], tail.data_ptr(),
+                tail[c.Q:].data_ptr(), err.data_ptr())
+        if not grid_pow:
+            self._call("ss_p_finish_dev", *args)
+            return
+        stream = self._stream()
+        if stream not in self._pow_work:
+            self._pow_work[stream] = self.torch.zeros(3, dtype=self.torch.int64, device=self.dev)
+        self._call("ss_p_finish_grid_dev", *args, self._pow_work[stream].data_ptr())
+
+    def _host_tail(self, c, grid_pow: bool = False):
         """The end of the transcript on the host: one download (channel, FRI roots, last layer), the last layer's mix,
-        the proof of work searched by ss_p_pow, the queries.  -> (roots, last, nonce, queries)"""
+        the proof of work searched by ss_p_pow, the queries.  -> (roots, last, nonce, queries)
+        grid_pow: ss_p_finish_grid_dev runs that end on the device over 2^(pow_bits + 8) nonces first, and the one
+        download brings its nonce and queries along; should it find none, the search below takes over."""
         torch = self.torch
         ch, K, L, pow_bits, hsel, mark = c.ch, c.K, c.L, c.pow_bits, c.hsel, c.mark
         g = self._Gather(self)
+        if grid_pow:
+            tail, err = self._empty(c.Q + 2), self._zeros(1)
+            self._finish(c, (1 << (64 - pow_bits)) - 1, 1 << (pow_bits + 8), tail, err, True)
+            k_tail, k_err = g.take(tail), g.take(err)
         k_state, k_roots, k_last = g.take(c.state), g.take(c.roots_dev), g.take(c.last)
         got = g.fetch()
+        if grid_pow and not int(got[k_err][0]) & 2:  # (bit 1, the last layer: raised below as ever)
+            roots = [got[k_roots][l].astype(">u4").tobytes() for l in range(K + 1)]
+            last_all = got[k_last]
+            if not (last_all == last_all[0]).all():
+                raise AssertionError("last FRI layer is not constant: the quotient is not low degree")
+            mark("fri commit")
+            mark("pow")
+            t = [int(x) for x in got[k_tail]]
+            return roots, tuple(int(x) for x in last_all[0]), (t[c.Q] << 32) | t[c.Q + 1], t[:c.Q]
         ch.digest = got[k_state][:8].astype(">u4").tobytes()
         ch.counter = int(got[k_state][8])
         roots = [got[k_roots][l].astype(">u4").tobytes() for l in range(K + 1)]
@@ -532,8 +564,10 @@ class GpuProver:
         return roots, last, nonce, queries[:c.Q]
 
     def prove_proof(self, n_cols: int = 4, trace_log: int = 9, log_blowup: int = 4, n_queries: int = 16,
-                    pow_bits: int = 5, seed: int = 0, hash: str = "sha256", fri_tail: bool = False):
-        """-> formats.StwoProof (arrays; what the verifier's record is made from).  fri_tail: see _commit."""
+                    pow_bits: int = 5, seed: int = 0, hash: str = "sha256", fri_tail: bool = False, grid_pow: bool = False):
+        """-> formats.StwoProof (arrays; what the verifier's record is made from).  fri_tail: see _commit.
+        grid_pow: the proof of work is ground by ss_p_finish_grid_dev (include/ss_prover_pow.h) instead of ss_p_pow's
+        spans of 2^22 with a download after each; the same proof."""
         c = self._commit(n_cols, trace_log, log_blowup, n_queries, pow_bits, seed, hash, fri_tail=fri_tail)
         N, n, L, K = c.N, c.n, c.L, c.K
         size_L, half_L = 1 << L, 1 << (L - 1)
@@ -541,7 +575,7 @@ class GpuProver:
                                                                       c.cp_tree, c.layers, c.trees)
         const_root, trace_root, cp_root, oods_trace, oods_cp = c.const_root, c.trace_root, c.cp_root, c.oods_trace, c.oods_cp
         mark, marks, t_start = c.mark, c.marks, c.t_start
-        roots, last, nonce, queries = self._host_tail(c)
+        roots, last, nonce, queries = self._host_tail(c, grid_pow)
         self.queries = list(queries)  # (of the last proof made by this call path; prove_minimal uses them)
         # every gather of the decommitment is enqueued first, then downloaded at once
         g = self._Gather(self)
@@ -608,7 +642,7 @@ class GpuProver:
         else:
             self._call("ss_p_decommit_minimal", *args, words_out.data_ptr())
 
-    def _enqueue_record(self, minimal: bool, out, words_out, pow_span: Optional[int], transcript: str, kw):
+    def _enqueue_record(self, minimal: bool, out, words_out, pow_span: Optional[int], transcript: str, grid_pow: bool, kw):
         """What prove_record and prove_minimal_record share: the protocol up to the FRI commit, ss_p_finish_dev, the
         decommitment into `out` (one record, or with `minimal` a row of ss_stwo_minimal_max_words words and the size
         word `words_out`), all enqueued and left pending for check()."""
@@ -627,17 +661,18 @@ class GpuProver:
                 words_out = self._empty(1)
             if words_out.dtype != self.torch.int32 or words_out.numel() != 1 or words_out.device != c.state.device:
                 raise ValueError("words_out must be one int32 word on the prover's device")
-        span = pow_span if pow_span is not None else 1 << min(22, c.pow_bits + 8)
+        # (grid_pow: 2^(pow_bits + 8) nonces hold none with probability e^-256, and the whole device searches them)
+        span = pow_span if pow_span is not None else 1 << (c.pow_bits + 8 if grid_pow else min(22, c.pow_bits + 8))
         if err is None:
             err = self._zeros(1)
         tail = self._empty(c.Q + 2)  # queries, nonce hi, lo
-        self._call("ss_p_finish_dev", c.hsel, c.L, c.Q, c.cs.pow_target, span, c.state.data_ptr(), c.last.data_ptr(),
-                   c.last.shape[0], tail.data_ptr(), tail[c.Q:].data_ptr(), err.data_ptr())
+        self._finish(c, c.cs.pow_target, span, tail, err, grid_pow)
         self._decommit_record(c, tail, tail[c.Q:], out, words_out)
         self._pending = (c, out, err, words_out)
         return out
 
-    def prove_record(self, out=None, pow_span: Optional[int] = None, check: bool = True, transcript: str = "host", **kw):
+    def prove_record(self, out=None, pow_span: Optional[int] = None, check: bool = True, transcript: str = "host",
+                     grid_pow: bool = False, **kw):
         """The proof of prove_proof(**kw) as the per-query record of include/ss_verify.h (verifier.stwo_record of it, word
         for word), written by the GPU into `out`: int32[record_words] on the device, e.g. a row of a caller's
         [n, record_words] tensor (allocated here when None; it may be uninitialised).  After the FRI commit nothing returns
@@ -649,14 +684,18 @@ class GpuProver:
         three draws, the OODS point and samples, the DEEP coefficients), so between the first launch and check() nothing
         is read from the device and nothing waits for it; `timings` then carries `total` only.  The same record.
         fri_tail=True (any entry of this class takes it): the FRI layers that fit in one workgroup are committed by one
-        launch (include/ss_prover_fri.h) instead of four to six launches each.  The same record again."""
-        out = self._enqueue_record(False, out, None, pow_span, transcript, kw)
+        launch (include/ss_prover_fri.h) instead of four to six launches each.  The same record again.
+        grid_pow=True (any entry of this class takes it): ss_p_finish_grid_dev (include/ss_prover_pow.h) takes the place
+        of ss_p_finish_dev -- the nonce is searched by a grid of workgroups over the whole device instead of one, and
+        the default `pow_span` is 2^(pow_bits + 8) with no cap, so a pow_bits of 20 to 30 stays on this route instead of
+        falling back to the host in check().  The same record again."""
+        out = self._enqueue_record(False, out, None, pow_span, transcript, grid_pow, kw)
         if check:
             self.check()
         return out
 
     def prove_minimal_record(self, out=None, words_out=None, pow_span: Optional[int] = None, check: bool = True,
-                             transcript: str = "host", **kw):
+                             transcript: str = "host", grid_pow: bool = False, **kw):
         """The proof of prove_proof(**kw) as the MINIMAL record of include/ss_verify_forms.h (verifier.stwo_minimal_record
         of formats.stwo_minimise of it, word for word), planned and gathered by the GPU (ss_p_decommit_minimal) behind the
         same _commit and ss_p_finish_dev as prove_record, with the same arguments.  A minimal record's size depends on the
@@ -665,7 +704,7 @@ class GpuProver:
         an element of a caller's [n] tensor) receives that size; nothing behind the record is written.  check=True reads
         the size together with the error word -- still one synchronisation -- and returns out[:words]; check=False returns
         the whole row, and words_out (and `record_words`) are valid once check() has returned."""
-        out = self._enqueue_record(True, out, words_out, pow_span, transcript, kw)
+        out = self._enqueue_record(True, out, words_out, pow_span, transcript, grid_pow, kw)
         if check:
             self.check()
             return out[:self.record_words]
@@ -827,12 +866,12 @@ class GpuProver:
         return stwo_minimise(proof, self.queries)
 
     def prove(self, n_cols: int = 4, trace_log: int = 9, log_blowup: int = 4, n_queries: int = 16,
-              pow_bits: int = 5, seed: int = 0, hash: str = "sha256", fri_tail: bool = False) -> dict:
+              pow_bits: int = 5, seed: int = 0, hash: str = "sha256", fri_tail: bool = False, grid_pow: bool = False) -> dict:
         """The same proof in the reference's `proof.json` schema (format C): `prove_proof` plus the
         conversion of 170 KB of hashes into JSON's lists of byte values (3-4 ms of pure Python at the
         2^20 shape, reported as timings["json"])."""
         from .formats import stwo_to_json
-        proof = self.prove_proof(n_cols, trace_log, log_blowup, n_queries, pow_bits, seed, hash, fri_tail)
+        proof = self.prove_proof(n_cols, trace_log, log_blowup, n_queries, pow_bits, seed, hash, fri_tail, grid_pow)
         t0 = time.perf_counter()
         out = stwo_to_json(proof)
         self.timings["json"] = time.perf_counter() - t0

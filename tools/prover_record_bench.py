@@ -1,18 +1,22 @@
 #!/usr/bin/env python3
-"""prove -> record-in-HBM, six routes alternating in one process on one MI355X:
+"""prove -> record-in-HBM, seven routes alternating in one process on one MI355X:
   host    prove_proof + verifier.stwo_record + upload          | prove_many(workers) + the same conversion
   device  prove_record (ss_p_finish_dev, ss_p_decommit_record) | prove_records(workers)
   devtx   prove_record(transcript="device"): the transcript before the FRI commit on the GPU as well
           (include/ss_prover_transcript.h)                     | prove_records(workers, transcript="device")
   fritail devtx with fri_tail=True: the FRI layers that fit in one workgroup committed by one launch
           (include/ss_prover_fri.h)                            | prove_records(workers, transcript="device", fri_tail=True)
+  gridpow devtx with grid_pow=True: the proof of work ground by a grid of workgroups over the whole device
+          (include/ss_prover_pow.h; span 2^(pow_bits + 8))      | prove_records(workers, transcript="device", grid_pow=True)
   minimal prove_minimal_record (ss_p_decommit_minimal): the MINIMAL record, planned and gathered on the device
                                                                | prove_minimal_records(workers): + ss_p_minimal_pack_dev
   minhost the minimal record without that kernel: prove_record, download, verifier.stwo_minimise_record, upload
           (the queries it needs are taken as known: replayed before the clock starts)   | prove_records + the same
-All end with the record(s) resident and the device synchronised; host / device / devtx / fritail must hold the same words, and so
-must minimal / minhost.
-`python tools/prover_record_bench.py [trace_log] [reps] [proofs] [workers] [n_cols]` (wide256: 14 15 48 4 256)."""
+All end with the record(s) resident and the device synchronised; host / device / devtx / fritail / gridpow must hold the same
+words, and so must minimal / minhost.
+`python tools/prover_record_bench.py [trace_log] [reps] [proofs] [workers] [n_cols] [pow_bits] [routes]` (wide256: 14 15 48 4
+256); `routes` = a comma-separated choice of the names above (default: all), e.g. `devtx,gridpow` at 20 bits, where devtx's
+search outgrows ss_p_finish_dev's span and falls back to the host."""
 import json
 import os
 import statistics
@@ -31,7 +35,9 @@ reps = int(sys.argv[2]) if len(sys.argv) > 2 else 15
 n_many = int(sys.argv[3]) if len(sys.argv) > 3 else 48
 workers = int(sys.argv[4]) if len(sys.argv) > 4 else 4
 n_cols = int(sys.argv[5]) if len(sys.argv) > 5 else 4
-kw = dict(n_cols=n_cols, trace_log=trace_log, log_blowup=4, n_queries=16, pow_bits=5, hash="sha256")
+pow_bits = int(sys.argv[6]) if len(sys.argv) > 6 else 5
+chosen = sys.argv[7].split(",") if len(sys.argv) > 7 else None
+kw = dict(n_cols=n_cols, trace_log=trace_log, log_blowup=4, n_queries=16, pow_bits=pow_bits, hash="sha256")
 gp = prover.GpuProver(verifier.Verifier(0))
 torch = gp.torch
 
@@ -44,7 +50,7 @@ def upload(proofs):
 
 cfg = gp.config(**kw)
 queries = []  # of seed i, for the minhost route
-for seed in range(n_many):
+for seed in range(n_many if chosen is None or "minhost" in chosen else 0):
     gp.prove_proof(seed=seed, **kw)
     queries.append(list(gp.queries))
 
@@ -71,15 +77,25 @@ routes = {
     "device_one": lambda: gp.prove_record(seed=0, **kw),
     "devtx_one": lambda: gp.prove_record(seed=0, transcript="device", **kw),
     "fritail_one": lambda: gp.prove_record(seed=0, transcript="device", fri_tail=True, **kw),
+    "gridpow_one": lambda: gp.prove_record(seed=0, transcript="device", grid_pow=True, **kw),
     "minimal_one": lambda: gp.prove_minimal_record(seed=0, **kw),
     "minhost_one": lambda: minimise_upload(gp.prove_record(seed=0, **kw)[None])[0],
     "host_many": lambda: upload(gp.prove_many(range(n_many), workers=workers, **kw)),
     "device_many": lambda: gp.prove_records(range(n_many), workers=workers, **kw),
     "devtx_many": lambda: gp.prove_records(range(n_many), workers=workers, transcript="device", **kw),
     "fritail_many": lambda: gp.prove_records(range(n_many), workers=workers, transcript="device", fri_tail=True, **kw),
+    "gridpow_many": lambda: gp.prove_records(range(n_many), workers=workers, transcript="device", grid_pow=True, **kw),
     "minimal_many": lambda: gp.prove_minimal_records(range(n_many), workers=workers, **kw),
     "minhost_many": lambda: minimise_upload(gp.prove_records(range(n_many), workers=workers, **kw)),
 }
+if chosen is not None:
+    routes = {k: v for k, v in routes.items() if k.rsplit("_", 1)[0] in chosen}
+
+
+def same(a, b):
+    return all(torch.equal(x, y) for x, y in zip(a, b)) if isinstance(a, tuple) else torch.equal(a, b)
+
+
 times = {k: [] for k in routes}
 for r in range(reps + 1):  # round 0 warms every route (allocator pools, worker streams, code objects)
     outs = {}
@@ -89,15 +105,13 @@ for r in range(reps + 1):  # round 0 warms every route (allocator pools, worker 
         dt, outs[name] = timed(fn)
         if r:
             times[name].append(dt / (n_many if name.endswith("many") else 1))
-    assert torch.equal(outs["host_one"], outs["device_one"]) and torch.equal(outs["host_one"], outs["devtx_one"])
-    assert torch.equal(outs["host_one"], outs["fritail_one"])
-    assert "host_many" not in outs or torch.equal(outs["host_many"], outs["fritail_many"])
-    assert "host_many" not in outs or (torch.equal(outs["host_many"], outs["device_many"]) and
-                                       torch.equal(outs["host_many"], outs["devtx_many"]))
-    assert torch.equal(outs["minimal_one"], outs["minhost_one"])
-    assert "minimal_many" not in outs or all(torch.equal(a, b) for a, b in zip(outs["minimal_many"], outs["minhost_many"]))
+    for group in (("host", "device", "devtx", "fritail", "gridpow"), ("minimal", "minhost")):
+        for suffix in ("_one", "_many"):
+            got = [outs[g + suffix] for g in group if g + suffix in outs]
+            assert all(same(got[0], x) for x in got[1:]), (group, suffix)
 result = {k: {"median_ms": 1e3 * statistics.median(v), "min_ms": 1e3 * min(v), "max_ms": 1e3 * max(v), "runs": len(v)}
           for k, v in times.items()}
 print(json.dumps({"metric": "prove -> resident record, 2^%d x %d, blowup 16, Q=16, per proof" % (trace_log, n_cols),
-                  "record_words": outs["device_one"].numel(), "minimal_words_seed0": outs["minimal_one"].numel(),
+                  "pow_bits": pow_bits, "record_words": next((v.numel() for k, v in outs.items() if k.endswith("_one") and not k.startswith("min")), None),
+                  "minimal_words_seed0": outs["minimal_one"].numel() if "minimal_one" in outs else None,
                   "proofs_in_many": n_many, "workers": workers, "routes": result}))
