@@ -40,6 +40,8 @@
 #include "ss_prover_fri.h"
 /* The end of the transcript with the proof of work ground by a grid of workgroups, in one launch.                  */
 #include "ss_prover_pow.h"
+/* A batch of small proofs, trace to record, in one launch: one workgroup per proof.                                */
+#include "ss_prover_small.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -111,6 +111,11 @@ def _be(words: Sequence[int]) -> bytes:
     return b"".join(int(w).to_bytes(4, "big") for w in words)
 
 
+class SmallTables(C.Structure):
+    """ss_p_small_tables (include/ss_prover_small.h)"""
+    _fields_ = [(k, C.c_void_p) for k in ("itw_n", "tw_c", "itw_c", "hxhy_c", "tw_l", "itw_l", "hxhy_l")]
+
+
 class GpuProver:
     """Proves on one MI355X through the ss_p_* kernels.  `ver` is a verifier.Verifier (it owns
     the library context and the device)."""
@@ -164,6 +169,13 @@ class GpuProver:
         L.ss_p_fri_tail_words.argtypes = [C.c_uint32, C.c_uint32]
         # include/ss_prover_pow.h
         sig("ss_p_finish_grid_dev", C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, u32p, u32p, sz, u32p, u32p, u32p, vp)
+        # include/ss_prover_small.h
+        sig("ss_p_prove_small_dev", C.POINTER(B.StwoCfg), C.c_uint64, C.c_uint64, vp, sz, sz, C.POINTER(SmallTables), u32p, vp, sz,
+            vp, sz, vp)
+        L.ss_p_small_limits.restype = None
+        L.ss_p_small_limits.argtypes = [C.POINTER(C.c_uint32)] * 3
+        L.ss_p_small_arena_words.restype = sz
+        L.ss_p_small_arena_words.argtypes = [C.POINTER(B.StwoCfg), sz]
         L.ss_p_eval_scratch_words.restype = sz
         L.ss_p_eval_scratch_words.argtypes = [C.c_uint32, C.c_uint32]
         self._dom: Dict[int, tuple] = {}
@@ -171,6 +183,7 @@ class GpuProver:
         self._workers: list = []  # (prover, stream) of prove_many
         self._pending = None  # (commit, record, error word, size word or None) of a prove_record / prove_minimal_record not yet checked
         self.record_words = None  # size of the last checked prove_minimal_record's record
+        self.small_errors = None  # the SS_P_ERR_* words of the last prove_records(one_launch=True), as the kernel left them
         self.timings: Dict[str, float] = {}
 
     # -- small helpers ---------------------------------------------------------------------
@@ -745,11 +758,19 @@ class GpuProver:
             prev = ts
         self.timings["total"] = prev - c.t_start
 
-    def prove_records(self, seeds: Sequence[int], workers: int = 4, **kw):
+    def prove_records(self, seeds: Sequence[int], workers: int = 4, one_launch: bool = False, n_groups: int = 0, **kw):
         """prove_record for every seed of `seeds` (keywords, transcript= included, are passed on) on the schedule of
         prove_many (the same worker streams and threads):
         -> int32[len(seeds), record_words] on the device, row i = the record of seeds[i], every row checked and the
-        device synchronised.  ss_stwo_pack_dev / Verifier.pack_stwo_records_dev take the tensor as it is."""
+        device synchronised.  ss_stwo_pack_dev / Verifier.pack_stwo_records_dev take the tensor as it is.
+        one_launch=True: the same tensor from ONE launch of ss_p_prove_small_dev (include/ss_prover_small.h), a workgroup
+        per proof on `n_groups` workgroups (0: two per compute unit), for the shapes within small_limits() -- a shape outside
+        them, or no seed at all, raises ValueError before anything is launched.  The seeds go up once and one error word
+        per proof comes back once (kept in `small_errors`); a proof whose nonce lies outside `pow_span` is redone through
+        prove_record.  `workers`, `transcript`, `fri_tail` and `grid_pow` choose among routes to the same words and mean
+        nothing here."""
+        if one_launch:
+            return self._prove_records_small(list(seeds), n_groups, **kw)
         seeds = list(seeds)
         if not seeds:
             return self._empty(0, 0)
@@ -763,12 +784,58 @@ class GpuProver:
         self._run_many(len(seeds), workers, one, t0)
         return rows
 
+    def small_limits(self) -> Tuple[int, int, int]:
+        """(lde_log, n_cols, n_queries): the largest that prove_records(one_launch=True) serves."""
+        lim = [C.c_uint32() for _ in range(3)]
+        self.lib.ss_p_small_limits(*[C.byref(x) for x in lim])
+        return tuple(int(x.value) for x in lim)
+
+    def _prove_records_small(self, seeds: List[int], n_groups: int = 0, pow_span: Optional[int] = None, n_cols: int = 4,
+                             trace_log: int = 9, log_blowup: int = 4, n_queries: int = 16, pow_bits: int = 5,
+                             hash: str = "sha256", transcript: str = "device", fri_tail: bool = False, grid_pow: bool = False):
+        torch = self.torch
+        from .verifier import MODE_FIXTURE, stwo_cfg_struct
+        shape = dict(n_cols=n_cols, trace_log=trace_log, log_blowup=log_blowup, n_queries=n_queries, pow_bits=pow_bits, hash=hash)
+        L = trace_log + log_blowup
+        max_l, max_n, max_q = self.small_limits()
+        if not (1 <= trace_log and 1 <= log_blowup and L <= max_l and 1 <= n_cols <= max_n and 1 <= n_queries <= max_q):
+            raise ValueError("one_launch serves lde_log <= %d, n_cols <= %d, n_queries <= %d (got %d, %d, %d)"
+                             % (max_l, max_n, max_q, L, n_cols, n_queries))
+        n = len(seeds)
+        if not n or hash not in HASHES or not 0 <= n_groups <= n or any(not 0 <= s < 1 << 63 for s in seeds):
+            raise ValueError("one_launch needs at least one seed in [0, 2^63), a known hash and n_groups <= len(seeds)")
+        t0 = time.perf_counter()
+        cs = stwo_cfg_struct(self.config(**shape), MODE_FIXTURE)
+        words = self.lib.ss_stwo_record_words(C.byref(cs))
+        if not n_groups:
+            n_groups = min(n, 2 * torch.cuda.get_device_properties(self.dev).multi_processor_count)
+        arena_words = self.lib.ss_p_small_arena_words(C.byref(cs), n_groups)
+        (_, itw_n, _), (tw_c, itw_c, hxhy_c), (tw_l, itw_l, hxhy_l) = self.domain(trace_log), self.domain(trace_log + 1), self.domain(L)
+        tables = SmallTables(*[x.data_ptr() for x in (itw_n, tw_c, itw_c, hxhy_c, tw_l, itw_l, hxhy_l)])
+        root = (C.c_uint32 * 8)(*np.frombuffer(HASHES[hash](b"").digest(), dtype=">u4"))
+        seeds_dev = torch.tensor(seeds, dtype=torch.int64).pin_memory().to(self.dev, non_blocking=True)
+        arena, rows, err = self._empty(arena_words), self._empty(n, words), self._empty(n)
+        span = pow_span if pow_span is not None else 1 << min(22, pow_bits + 8)
+        self._call("ss_p_prove_small_dev", C.byref(cs), cs.pow_target, span, seeds_dev.data_ptr(), n, n_groups, C.byref(tables),
+                   root, arena.data_ptr(), arena_words, rows.data_ptr(), words, err.data_ptr())
+        self.small_errors = bits = self._host(err).copy()  # the one read: it waits for the launch
+        if (bits & 4).any():
+            raise AssertionError("transcript: a draw ran out of tries, or 1 + t^2 has no inverse")
+        if (bits & 1).any():
+            raise AssertionError("last FRI layer is not constant: the quotient is not low degree")
+        for i in np.flatnonzero(bits & 2):  # no nonce in the span: the existing route, whose check() searches on
+            self.prove_record(out=rows[int(i)], seed=seeds[int(i)], pow_span=span, transcript="device", **shape)
+        dt = time.perf_counter() - t0
+        self.timings = {"total": dt, "proofs_per_s": n / dt, "groups": n_groups}
+        return rows
+
     def prove_minimal_records(self, seeds: Sequence[int], workers: int = 4, **kw):
         """prove_minimal_record for every seed of `seeds` on the schedule of prove_records, then packed on the device
         (ss_p_minimal_pack_dev): every proof writes a row of an [n, max_words] tensor and a word of an [n] size tensor, a
         scan of the sizes gives the offsets and a copy lays the records back to back.
         -> (records, offs): int32[offs[n]] and int64[n + 1] on the device, record i = records[offs[i]:offs[i + 1]], every
-        proof checked and the device synchronised.  verifier.StwoMinimalDeviceBatch takes the pair as it is."""
+        proof checked and the device synchronised.  verifier.StwoMinimalDeviceBatch takes the pair as it is.
+        (There is no one_launch= here: the one-launch kernel of prove_records writes per-query records only.)"""
         torch = self.torch
         seeds = list(seeds)
         n = len(seeds)
