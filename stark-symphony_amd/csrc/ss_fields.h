@@ -207,6 +207,10 @@ __device__ __forceinline__ uint32_t m31_mul_c(uint32_t a, uint32_t b)
     const uint32_t s = (lo & M31_P) + __funnelshift_r(lo, hi, 31);        // x0 + (x >> 31) <= 2P
     return min(s, s - M31_P);
 }
+__device__ __forceinline__ QM31 qm31_add_c(QM31 x, QM31 y)
+{
+    return {m31_add_c(x.a, y.a), m31_add_c(x.b, y.b), m31_add_c(x.c, y.c), m31_add_c(x.d, y.d)};
+}
 __device__ __forceinline__ QM31 qm31_red(QM31 x) { return {m31_red(x.a), m31_red(x.b), m31_red(x.c), m31_red(x.d)}; }
 
 // ------------------------------------------------------ groups/m31_point.simf:33-97

@@ -6,50 +6,24 @@
 // bits as the numpy code.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-
 #include "../../include/ss_prover.h"
-#include "ss_channel.h"
 #include "ss_ctx.h"
-#include "ss_fields.h"
-#include "ss_hash.h"
-#include "ss_layout.h"
+#include "ss_prover_dev.h"
 
 using namespace ss;
 
 extern "C" int ss_internal_set_err(int code, const char *msg);
 
-#define P_TRY(expr)                                                                  \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess) {                                                      \
-            char buf_[256];                                                          \
-            snprintf(buf_, sizeof buf_, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            return ss_internal_set_err(SS_ERR_HIP, buf_);                            \
-        }                                                                            \
-    } while (0)
-
 static inline unsigned blocks_for(uint64_t n, unsigned bs = 256) { return (unsigned)((n + bs - 1) / bs); }
 
 namespace ss {
-
-__device__ __forceinline__ QM31 ldq(const uint32_t *p) { return QM31{p[0], p[1], p[2], p[3]}; }
-__device__ __forceinline__ void stq(uint32_t *p, QM31 v) { p[0] = v.a; p[1] = v.b; p[2] = v.c; p[3] = v.d; }
 
 // ---------------------------------------------------------------------------------- trace
 __global__ void p_trace_kernel(uint32_t n, uint32_t n_cols, uint32_t seed_term, uint32_t *__restrict__ out)
 {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
-    uint32_t a = 1, b = m31_add(m31_red(r), seed_term);
-    out[r] = a;
-    if (n_cols > 1) out[(size_t)n + r] = b;
-    for (uint32_t k = 2; k < n_cols; k++) {
-        uint32_t c = m31_add(m31_sqr(b), m31_sqr(a));
-        out[(size_t)k * n + r] = c;
-        a = b;
-        b = c;
-    }
+    trace_row(r, seed_term, n_cols, n, out);
 }
 
 // ------------------------------------------------------------------------------- twiddles
@@ -524,9 +498,7 @@ __global__ void p_hash_rows_kernel(size_t n, uint32_t w, const uint32_t *__restr
     } else {
         Hasher<HF>::template stream<true, 0>(nullptr, [&](uint32_t k) { return cols[(size_t)k * stride + i]; }, WC ? WC : w, d);
     }
-    uint4 *o = reinterpret_cast<uint4 *>(out + i * 8);
-    o[0] = make_uint4(Hasher<HF>::native(d[0]), Hasher<HF>::native(d[1]), Hasher<HF>::native(d[2]), Hasher<HF>::native(d[3]));
-    o[1] = make_uint4(Hasher<HF>::native(d[4]), Hasher<HF>::native(d[5]), Hasher<HF>::native(d[6]), Hasher<HF>::native(d[7]));
+    st_node<HF>(out, i, d);
 }
 
 template <int HF>
@@ -538,9 +510,7 @@ __global__ void p_hash_qm31_kernel(size_t n, const uint32_t *__restrict__ vals, 
     const uint32_t e[4] = {v.x, v.y, v.z, v.w};
     uint32_t d[8];
     Hasher<HF>::template block<true, 0, 4>(nullptr, e, d);
-    uint4 *o = reinterpret_cast<uint4 *>(out + i * 8);
-    o[0] = make_uint4(Hasher<HF>::native(d[0]), Hasher<HF>::native(d[1]), Hasher<HF>::native(d[2]), Hasher<HF>::native(d[3]));
-    o[1] = make_uint4(Hasher<HF>::native(d[4]), Hasher<HF>::native(d[5]), Hasher<HF>::native(d[6]), Hasher<HF>::native(d[7]));
+    st_node<HF>(out, i, d);
 }
 
 template <int HF>
@@ -573,19 +543,10 @@ __global__ void __launch_bounds__(256) p_merkle_tail_kernel(uint32_t n, uint32_t
 template <int HF>
 __device__ __forceinline__ void merkle_parent(size_t i, const uint32_t *children, uint32_t *parents)
 {
-    const uint4 *c = reinterpret_cast<const uint4 *>(children + i * 16);
-    const uint4 a0 = c[0], a1 = c[1], b0 = c[2], b1 = c[3];
-    const uint32_t l[8] = {Hasher<HF>::native(a0.x), Hasher<HF>::native(a0.y), Hasher<HF>::native(a0.z),
-                           Hasher<HF>::native(a0.w), Hasher<HF>::native(a1.x), Hasher<HF>::native(a1.y),
-                           Hasher<HF>::native(a1.z), Hasher<HF>::native(a1.w)};
-    const uint32_t r[8] = {Hasher<HF>::native(b0.x), Hasher<HF>::native(b0.y), Hasher<HF>::native(b0.z),
-                           Hasher<HF>::native(b0.w), Hasher<HF>::native(b1.x), Hasher<HF>::native(b1.y),
-                           Hasher<HF>::native(b1.z), Hasher<HF>::native(b1.w)};
+    const Dig l = ld_node<HF>(children, 2 * i), r = ld_node<HF>(children, 2 * i + 1);
     uint32_t d[8];
-    Hasher<HF>::template pair<true>(l, r, d);
-    uint4 *o = reinterpret_cast<uint4 *>(parents + i * 8);
-    o[0] = make_uint4(Hasher<HF>::native(d[0]), Hasher<HF>::native(d[1]), Hasher<HF>::native(d[2]), Hasher<HF>::native(d[3]));
-    o[1] = make_uint4(Hasher<HF>::native(d[4]), Hasher<HF>::native(d[5]), Hasher<HF>::native(d[6]), Hasher<HF>::native(d[7]));
+    Hasher<HF>::template pair<true>(l.v, r.v, d);
+    st_node<HF>(parents, i, d);
 }
 
 // parent[i] = H(leaf[i] || leaf[i]): a tree whose leaves come in equal pairs
@@ -594,55 +555,26 @@ __global__ void p_merkle_dup_kernel(size_t n, const uint32_t *__restrict__ leaf,
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint4 *c = reinterpret_cast<const uint4 *>(leaf + i * 8);
-    const uint4 a0 = c[0], a1 = c[1];
-    const uint32_t l[8] = {Hasher<HF>::native(a0.x), Hasher<HF>::native(a0.y), Hasher<HF>::native(a0.z),
-                           Hasher<HF>::native(a0.w), Hasher<HF>::native(a1.x), Hasher<HF>::native(a1.y),
-                           Hasher<HF>::native(a1.z), Hasher<HF>::native(a1.w)};
+    const Dig l = ld_node<HF>(leaf, i);
     uint32_t d[8];
-    Hasher<HF>::template pair<true>(l, l, d);
-    uint4 *o = reinterpret_cast<uint4 *>(parents + i * 8);
-    o[0] = make_uint4(Hasher<HF>::native(d[0]), Hasher<HF>::native(d[1]), Hasher<HF>::native(d[2]), Hasher<HF>::native(d[3]));
-    o[1] = make_uint4(Hasher<HF>::native(d[4]), Hasher<HF>::native(d[5]), Hasher<HF>::native(d[6]), Hasher<HF>::native(d[7]));
+    Hasher<HF>::template pair<true>(l.v, l.v, d);
+    st_node<HF>(parents, i, d);
 }
 
 // ----------------------------------------------------------------------------- composition
-__device__ __forceinline__ void composition_row(uint32_t n_log, uint32_t n_cols, const uint32_t *__restrict__ ev,
-                                                const uint32_t *__restrict__ hx, QM31 alpha, uint32_t *__restrict__ out)
-{
-    const uint32_t size = 1u << (n_log + 1);
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= size) return;
-    uint32_t van = hx[i >> 1];
-    for (uint32_t k = 1; k < n_log; k++) van = m31_dbl_x(van);
-    uint32_t van_inv;
-    m31_inv(van, van_inv);
-    QM31 acc = qm31_zero();
-    uint32_t a = ev[i], b = n_cols > 1 ? ev[(size_t)size + i] : 0;
-    for (uint32_t k = 2; k < n_cols; k++) {
-        const uint32_t c = ev[(size_t)k * size + i];
-        const uint32_t cons = m31_sub(c, m31_add(m31_sqr(b), m31_sqr(a)));
-        acc = qm31_mul(acc, alpha);
-        acc.a = m31_add(acc.a, cons);
-        a = b;
-        b = c;
-    }
-    out[i] = m31_mul(acc.a, van_inv);
-    out[(size_t)size + i] = m31_mul(acc.b, van_inv);
-    out[(size_t)2 * size + i] = m31_mul(acc.c, van_inv);
-    out[(size_t)3 * size + i] = m31_mul(acc.d, van_inv);
-}
 __global__ void p_composition_kernel(uint32_t n_log, uint32_t n_cols, const uint32_t *__restrict__ ev,
                                      const uint32_t *__restrict__ hx, QM31 alpha, uint32_t *__restrict__ out)
 {
-    composition_row(n_log, n_cols, ev, hx, alpha, out);
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (1u << (n_log + 1))) composition_point(i, n_log, n_cols, ev, hx, alpha, out);
 }
 // the same rows with alpha read from device memory (written by ss_p_channel_begin_dev): a uniform load
 __global__ void p_composition_dev_kernel(uint32_t n_log, uint32_t n_cols, const uint32_t *__restrict__ ev,
                                          const uint32_t *__restrict__ hx, const uint32_t *__restrict__ alpha_dev,
                                          uint32_t *__restrict__ out)
 {
-    composition_row(n_log, n_cols, ev, hx, ldq(alpha_dev), out);
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (1u << (n_log + 1))) composition_point(i, n_log, n_cols, ev, hx, ldq(alpha_dev), out);
 }
 
 // -------------------------------------------------------------------------- eval at point
@@ -693,121 +625,26 @@ __global__ void p_channel_fri_layer_kernel(uint32_t *__restrict__ state, const u
 {
     if (blockIdx.x || threadIdx.x) return;
     Channel<HF> ch;
-    for (int i = 0; i < 8; i++) ch.dig.v[i] = Hasher<HF>::native(state[i]);
-    ch.ctr = state[8];
+    channel_load(ch, state);
     uint32_t r[8];
     for (int i = 0; i < 8; i++) { r[i] = root[i]; root_out[i] = r[i]; }
     ch.mix(r);
     QM31 a;
     ch.draw_qm31(a);
     stq(alpha_out, a);
-    for (int i = 0; i < 8; i++) state[i] = Hasher<HF>::native(ch.dig.v[i]);
-    state[8] = ch.ctr;
+    channel_store(ch, state);
 }
 
 // ------------------------------------------------------------------------------ quotients
-struct QuotArgs {
-    QM31 px, py, p2x, p2y, a1, c1, a2, c2, alpha16;
-};
-
-__device__ __forceinline__ CM31 deep_den_inv(QM31 sx, QM31 sy, uint32_t x, uint32_t y)
-{
-    // deep/quotients.simf:15-22
-    CM31 dx = cm31_sub_m31(q_re(sx), x), dy = cm31_sub_m31(q_re(sy), y);
-    CM31 d = cm31_sub(cm31_mul(dx, q_im(sy)), cm31_mul(dy, q_im(sx)));
-    CM31 inv;
-    cm31_inv(d, inv);
-    return inv;
-}
-
-// One thread = the storage pair (2h, 2h+1): the two positions share x and have y, -y.  The column
-// sums are open 64-bit multiply-accumulates (one v_mad_u64_u32 per product, folded every third
-// product, reduced once per word); the four DEEP denominators (two sample points x two positions)
-// share ONE M31 inversion.  All operands are canonical field elements, so every re-association gives
-// the bits of the straightforward evaluation (which tools/stwo_prover.py performs).
-__device__ __forceinline__ void
-quotients_pair(uint32_t lde_log, uint32_t n_cols, const uint32_t *__restrict__ trace_lde,
-               const uint32_t *__restrict__ cp_lde, uint32_t cp_log, const uint32_t *__restrict__ hx,
-               const uint32_t *__restrict__ hy, const uint32_t *__restrict__ bcoef, const QuotArgs &q,
-               uint32_t *__restrict__ out)
-{
-    const size_t size = (size_t)1 << lde_log;
-    const size_t h = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (h >= (size >> 1)) return;
-    const uint32_t x = hx[h], y0 = hy[h];
-    const uint32_t ys[2] = {y0, m31_sub_c(0, y0)};
-    // s[batch][position] = sum_k b_k v_k
-    // (pairs = false: a column that depends on x only holds ONE value per storage pair, stride size / 2)
-    auto dot = [&](const uint32_t *lde, const uint32_t *coef, uint32_t count, bool pairs, QM31 (&res)[2]) {
-        uint64_t acc[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-        uint32_t open = 0;
-        for (uint32_t k = 0; k < count; k++) {
-            uint2 v;
-            if (pairs) v = *reinterpret_cast<const uint2 *>(lde + (size_t)k * size + 2 * h);
-            else v.x = v.y = lde[(size_t)k * (size >> 1) + h];
-            const uint4 c = *reinterpret_cast<const uint4 *>(coef + 4 * k);
-            acc[0][0] = m31_mac(acc[0][0], c.x, v.x); acc[0][1] = m31_mac(acc[0][1], c.y, v.x);
-            acc[0][2] = m31_mac(acc[0][2], c.z, v.x); acc[0][3] = m31_mac(acc[0][3], c.w, v.x);
-            if (pairs) {  // (one value per pair: the second sum is the first)
-                acc[1][0] = m31_mac(acc[1][0], c.x, v.y); acc[1][1] = m31_mac(acc[1][1], c.y, v.y);
-                acc[1][2] = m31_mac(acc[1][2], c.z, v.y); acc[1][3] = m31_mac(acc[1][3], c.w, v.y);
-            }
-            if (++open == 3) {
-#pragma unroll
-                for (int p = 0; p < 2; p++)
-#pragma unroll
-                    for (int w = 0; w < 4; w++) acc[p][w] = m31_fold62(acc[p][w]);
-                open = 0;
-            }
-        }
-#pragma unroll
-        for (int p = 0; p < 2; p++)
-            res[p] = QM31{m31_red64(acc[p][0]), m31_red64(acc[p][1]), m31_red64(acc[p][2]), m31_red64(acc[p][3])};
-        if (!pairs) res[1] = res[0];
-    };
-    QM31 s1[2], s2[2];
-    dot(trace_lde, bcoef, n_cols, true, s1);
-    dot(cp_lde, bcoef + 4 * n_cols, kCp, cp_log == lde_log, s2);
-    // deep_quotient_denominator_inverse (deep/quotients.simf:15-22) for (P, 2P) x (y, -y)
-    CM31 d[4];
-    uint32_t nrm[4], pre[4];
-    uint32_t run = 1;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const QM31 sx = j < 2 ? q.px : q.p2x, sy = j < 2 ? q.py : q.p2y;
-        const CM31 dx = cm31_sub_m31(q_re(sx), x), dy = cm31_sub_m31(q_re(sy), ys[j & 1]);
-        d[j] = cm31_sub(cm31_mul(dx, q_im(sy)), cm31_mul(dy, q_im(sx)));
-        nrm[j] = m31_add(m31_sqr(d[j].a), m31_sqr(d[j].b));
-        pre[j] = run;
-        run = m31_mul(run, nrm[j] ? nrm[j] : 1u);  // a zero norm inverts to 0, as cm31_inv gives
-    }
-    uint32_t inv;
-    m31_inv(run, inv);
-    CM31 dinv[4];
-#pragma unroll
-    for (int j = 3; j >= 0; j--) {
-        const uint32_t ni = nrm[j] ? m31_mul(inv, pre[j]) : 0u;
-        inv = m31_mul(inv, nrm[j] ? nrm[j] : 1u);
-        dinv[j] = cm31_mul_m31(CM31{d[j].a, m31_neg(d[j].b)}, ni);
-    }
-    const QM31 a1y = qm31_mul_m31(q.a1, y0), a2y = qm31_mul_m31(q.a2, y0);
-#pragma unroll
-    for (int p = 0; p < 2; p++) {
-        // a * (-y) = -(a * y)
-        const QM31 t1 = p ? qm31_sub(q.c1, a1y) : qm31_add(a1y, q.c1);
-        const QM31 t2 = p ? qm31_sub(q.c2, a2y) : qm31_add(a2y, q.c2);
-        const QM31 b1 = qm31_mul_cm31(qm31_sub(s1[p], t1), dinv[p]);
-        const QM31 b2 = qm31_mul_cm31(qm31_sub(s2[p], t2), dinv[2 + p]);
-        stq(out + 4 * (2 * h + p), qm31_add(qm31_mul(b1, q.alpha16), b2));
-    }
-}
+// One thread = one storage pair (quotients_pair, ss_prover_dev.h).
 __global__ void __launch_bounds__(256)
 p_quotients_kernel(uint32_t lde_log, uint32_t n_cols, const uint32_t *__restrict__ trace_lde,
                    const uint32_t *__restrict__ cp_lde, uint32_t cp_log, const uint32_t *__restrict__ hx,
                    const uint32_t *__restrict__ hy, const uint32_t *__restrict__ bcoef, QuotArgs q,
                    uint32_t *__restrict__ out)
 {
-    quotients_pair(lde_log, n_cols, trace_lde, cp_lde, cp_log, hx, hy, bcoef, q, out);
+    const size_t h = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (h < ((size_t)1 << (lde_log - 1))) quotients_pair(h, lde_log, n_cols, trace_lde, cp_lde, cp_log, hx, hy, bcoef, q, out);
 }
 // The same pairs with the nine scalars read from device memory (points: px, py, p2x, p2y as ss_p_oods_point_dev writes
 // them; sums: A1, C1, A2, C2, alpha^16 as ss_p_deep_coeffs_dev does).  The 36 addresses do not depend on the lane, so
@@ -818,10 +655,9 @@ p_quotients_dev_kernel(uint32_t lde_log, uint32_t n_cols, const uint32_t *__rest
                        const uint32_t *__restrict__ hy, const uint32_t *__restrict__ bcoef,
                        const uint32_t *__restrict__ points, const uint32_t *__restrict__ sums, uint32_t *__restrict__ out)
 {
-    QuotArgs q;
-    q.px = ldq(points); q.py = ldq(points + 4); q.p2x = ldq(points + 8); q.p2y = ldq(points + 12);
-    q.a1 = ldq(sums); q.c1 = ldq(sums + 4); q.a2 = ldq(sums + 8); q.c2 = ldq(sums + 12); q.alpha16 = ldq(sums + 16);
-    quotients_pair(lde_log, n_cols, trace_lde, cp_lde, cp_log, hx, hy, bcoef, q, out);
+    const size_t h = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (h < ((size_t)1 << (lde_log - 1)))
+        quotients_pair(h, lde_log, n_cols, trace_lde, cp_lde, cp_log, hx, hy, bcoef, quot_args(points, sums), out);
 }
 
 // ------------------------------------------------------------------------------- fri fold
@@ -830,10 +666,7 @@ __global__ void p_fri_fold_kernel(size_t n_out, const uint32_t *__restrict__ in,
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_out) return;
-    const QM31 v0 = ldq(in + 8 * i), v1 = ldq(in + 8 * i + 4);
-    const QM31 f0 = qm31_add(v0, v1);
-    const QM31 f1 = qm31_mul_m31(qm31_sub(v0, v1), cinv[i]);
-    stq(out + 4 * i, qm31_add(f0, qm31_mul(f1, alpha)));
+    stq(out + 4 * i, fri_fold(ldq(in + 8 * i), ldq(in + 8 * i + 4), cinv[i], alpha));
 }
 
 // the same fold with alpha read from device memory (written by p_channel_fri_layer_kernel)
@@ -842,11 +675,7 @@ __global__ void p_fri_fold_dev_kernel(size_t n_out, const uint32_t *__restrict__
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_out) return;
-    const QM31 alpha = ldq(alpha_dev);
-    const QM31 v0 = ldq(in + 8 * i), v1 = ldq(in + 8 * i + 4);
-    const QM31 f0 = qm31_add(v0, v1);
-    const QM31 f1 = qm31_mul_m31(qm31_sub(v0, v1), cinv[i]);
-    stq(out + 4 * i, qm31_add(f0, qm31_mul(f1, alpha)));
+    stq(out + 4 * i, fri_fold(ldq(in + 8 * i), ldq(in + 8 * i + 4), cinv[i], ldq(alpha_dev)));
 }
 
 // ------------------------------------------------------------------------------------ pow
@@ -880,52 +709,21 @@ p_finish_kernel(uint32_t *__restrict__ state, const uint32_t *__restrict__ last,
     __shared__ unsigned long long best;
     constexpr unsigned long long kNone = ~0ull;
     const uint32_t tid = threadIdx.x;
-    const uint4 *rows = reinterpret_cast<const uint4 *>(last);
-    const uint4 first = rows[0];
-    int differs = 0;
-    for (size_t i = tid; i < n_last; i += kFinishThreads) {
-        const uint4 v = rows[i];
-        differs |= (v.x != first.x) | (v.y != first.y) | (v.z != first.z) | (v.w != first.w);
-    }
+    const int differs = last_layer_differs(last, n_last, tid, kFinishThreads);
+    const QM31 first = ldq4(last);
     Channel<HF> ch;
-#pragma unroll
-    for (int i = 0; i < 8; i++) ch.dig.v[i] = Hasher<HF>::native(state[i]);
-    ch.ctr = state[8];
+    channel_load(ch, state);
     if (tid == 0) best = kNone;
     const int bad_layer = __syncthreads_or(differs);  // (also: every lane has read `state`, `best` is set)
-    const uint32_t lv[4] = {first.x, first.y, first.z, first.w};
+    const uint32_t lv[4] = {first.a, first.b, first.c, first.d};
     ch.mix_values(lv);
-    unsigned long long nonce = kNone;
-    for (uint64_t base = 0; base < span; base += kFinishThreads) {
-        const uint64_t cand = base + tid;
-        if (cand < span) {
-            const uint32_t m[2] = {(uint32_t)(cand >> 32), (uint32_t)cand};
-            uint32_t d[8];
-            Hasher<HF>::template block<true, 8, 2>(ch.dig.v, m, d);
-            if (Hasher<HF>::pow_value(d) < target) atomicMin(&best, (unsigned long long)cand);
-        }
-        __syncthreads();
-        nonce = best;
-        __syncthreads();  // (nobody enters the next round's atomicMin before everybody has read this round's result)
-        if (nonce != kNone) break;
-    }
+    const unsigned long long nonce = pow_search_workgroup<HF, true>(ch.dig.v, target, span, &best, tid, kFinishThreads);
     if (nonce != kNone) {
         const uint32_t nv[2] = {(uint32_t)(nonce >> 32), (uint32_t)nonce};
         ch.mix_values(nv);
-        const uint32_t mask = (uint32_t)(((uint64_t)1 << lde_log) - 1);
-        for (uint32_t got = 0; got < n_queries; got += 8) {
-            uint32_t w[8];
-            ch.draw_words(w);
-            if (tid == 0) {
-#pragma unroll
-                for (uint32_t k = 0; k < 8; k++)
-                    if (got + k < n_queries) queries[got + k] = w[k] & mask;
-            }
-        }
+        draw_queries<HF, false>(ch, lde_log, n_queries, tid == 0, queries);
         if (tid == 0) {
-#pragma unroll
-            for (int i = 0; i < 8; i++) state[i] = Hasher<HF>::native(ch.dig.v[i]);
-            state[8] = ch.ctr;
+            channel_store(ch, state);
             nonce_out[0] = nv[0];
             nonce_out[1] = nv[1];
         }
@@ -953,16 +751,6 @@ struct DecommitArgs {
 };
 constexpr uint32_t kDecommitThreads = 256, kDecommitChains = kDecommitThreads / 64;
 
-__device__ __forceinline__ void move16(uint32_t *dst, const uint32_t *src)
-{
-    const uint4 v = *reinterpret_cast<const uint4 *>(src);
-    if (((uintptr_t)dst & 15) == 0) {
-        *reinterpret_cast<uint4 *>(dst) = v;
-    } else {
-        dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
-    }
-}
-
 __global__ void __launch_bounds__(kDecommitThreads)
 p_decommit_record_kernel(DecommitArgs a, const ss_p_tree *__restrict__ trees_dev, const uint32_t *__restrict__ samples,
                          const uint32_t *__restrict__ fri_roots, const uint32_t *__restrict__ last,
@@ -974,65 +762,20 @@ p_decommit_record_kernel(DecommitArgs a, const ss_p_tree *__restrict__ trees_dev
     for (uint32_t i = tid; i < kinds; i += kDecommitThreads) trees[i] = trees_dev[i];
     if (tid < Q) qs[tid] = queries[tid] & (uint32_t)(((uint64_t)1 << L) - 1);
     __syncthreads();
-    const uint32_t oods = 4 * (N + kCp), head = 24 + oods + 8 * (K + 1) + 6;  // roots, samples, FRI roots, last layer, nonce
-    const uint32_t per_q = N + kCp + 16 * L;
     if (blockIdx.x == gridDim.x - 1) {
         // ---- head and trailer
-        const uint32_t *troot = trees[0].levels + (((uint64_t)2 << L) - 2) * 8;
-        const uint32_t *croot = trees[1].levels + (((uint64_t)1 << L) - 2) * 8;  // (tree over the 2^(L-1) pairs)
-        for (uint32_t w = tid; w < head; w += kDecommitThreads) {
-            uint32_t v = 0, r = w;
-            if (r < 8) {
-#pragma unroll
-                for (uint32_t k = 0; k < 8; k++)  // (a kernel argument: selected, not indexed)
-                    if (r == k) v = a.const_root.v[k];
-            }
-            else if ((r -= 8) < 8) v = troot[r];
-            else if ((r -= 8) < 8) v = croot[r];
-            else if ((r -= 8) < oods) v = samples[r];
-            else if ((r -= oods) < 8 * (K + 1)) v = fri_roots[r];
-            else if ((r -= 8 * (K + 1)) < 4) v = last[r];
-            else v = nonce[r - 4];
-            rec[w] = v;
-        }
+        const RecordHead hd = {a.const_root, trees[0].levels + (((uint64_t)2 << L) - 2) * 8,
+                               trees[1].levels + (((uint64_t)1 << L) - 2) * 8,  // (tree over the 2^(L-1) pairs)
+                               samples, fri_roots, last, nonce};
+        for (uint32_t w = tid; w < record_head_words(N, K); w += kDecommitThreads) rec[w] = record_head_word(w, hd, N, K);
         uint32_t *plen = rec + stwo_record_words(N, L, Q, K) - (uint64_t)kinds * Q;
-        for (uint32_t i = tid; i < kinds * Q; i += kDecommitThreads) {
-            const uint32_t kind = i / Q;
-            plen[i] = kind < 2 ? L : L + 1 - kind;
-        }
+        for (uint32_t i = tid; i < kinds * Q; i += kDecommitThreads) plen[i] = record_path_len(i, L, Q);
         return;
     }
     const uint32_t lane = tid & 63, chain = blockIdx.x * kDecommitChains + (tid >> 6);
     if (chain >= kinds * Q) return;
-    const uint32_t kind = chain / Q, q = chain - kind * Q, idx = qs[q];
-    const ss_p_tree t = trees[kind];
-    // the chain's tree has 2^m leaves, the chain enters it at position p, and its sibling s is tree level s + first
-    // (composition: sibling 0 is the pair's other leaf, the same hash, and the tree over the pairs starts above it)
-    uint32_t m, p, len, *dst;
-    int first;
-    if (kind == 0) {
-        uint32_t *slot = rec + head + (size_t)q * per_q;
-        for (uint32_t c = lane; c < N; c += 64) slot[c] = t.values[((size_t)c << L) + idx];
-        m = L; p = idx; len = L; first = 0; dst = slot + N + kCp;
-    } else if (kind == 1) {
-        uint32_t *slot = rec + head + (size_t)q * per_q + N;
-        if (lane < kCp) slot[lane] = t.values[((size_t)lane << (L - 1)) + (idx >> 1)];
-        m = L - 1; p = idx >> 1; len = L; first = -1; dst = slot + kCp + 8 * L;
-    } else {
-        const uint32_t l = kind - 2;
-        len = L - 1 - l;
-        // layers 0 .. l-1 hold Q (4 + 8 (L - 1 - l')) words each
-        const uint32_t before = Q * (4 * l + 8 * (l * (L - 1) - l * (l - 1) / 2));
-        uint32_t *slot = rec + head + (size_t)Q * per_q + before + (size_t)q * (4 + 8 * len);
-        m = L - l; p = idx >> l; first = 1; dst = slot + 4;
-        if (lane == 0) move16(slot, t.values + (size_t)(p ^ 1) * 4);
-    }
-    const uint64_t two_n = (uint64_t)2 << m;
-    for (uint32_t s = lane >> 1; s < len; s += 32) {
-        const int j = (int)s + first;
-        const uint32_t *src = j < 0 ? t.leaf + (size_t)p * 8 : t.levels + (two_n - (two_n >> j) + ((p >> j) ^ 1)) * 8;
-        move16(dst + s * 8 + (lane & 1) * 4, src + (lane & 1) * 4);
-    }
+    const uint32_t kind = chain / Q, q = chain - kind * Q;
+    record_chain(kind, q, qs[q], lane, trees[kind], N, L, Q, K, rec);
 }
 
 }  // namespace ss
@@ -1048,7 +791,7 @@ extern "C" int ss_p_trace(ss_ctx *ctx, uint32_t n_log, uint32_t n_cols, uint32_t
     const uint32_t n = 1u << n_log;
     hipLaunchKernelGGL(p_trace_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, n, n_cols,
                        seed_term % M31_P, cols_out);
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1059,7 +802,7 @@ extern "C" int ss_p_twiddles(ss_ctx *ctx, uint32_t m, uint32_t *tw_out, uint32_t
     if (!tw_out || !itw_out || m < 1 || m > 28) return ss_internal_set_err(SS_ERR_ARG, "ss_p_twiddles: bad argument");
     hipLaunchKernelGGL(p_twiddles_kernel, dim3(blocks_for(1u << (m - 1))), dim3(256), 0, (hipStream_t)stream, m,
                        tw_out, itw_out, hx_out);
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1084,7 +827,7 @@ extern "C" int ss_p_fft(ss_ctx *ctx, uint32_t m, uint32_t ncols, uint32_t *data,
             else
                 launch_strided_pass(m, lo[i], nb[i], ncols, data, tw, inverse, scale, nullptr, 0u, (hipStream_t)stream);
         }
-        P_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         return SS_OK;
     }
     const dim3 grid(blocks_for(1u << (m - 1)), ncols);
@@ -1096,7 +839,7 @@ extern "C" int ss_p_fft(ss_ctx *ctx, uint32_t m, uint32_t ncols, uint32_t *data,
         for (uint32_t i = m; i-- > 0;)
             hipLaunchKernelGGL(p_fft_layer_kernel, grid, dim3(256), 0, (hipStream_t)stream, m, i, data, tw, 0, 1u);
     }
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1114,9 +857,9 @@ extern "C" int ss_p_lde(ss_ctx *ctx, uint32_t k, uint32_t m, uint32_t ncols, con
     // the shortcut needs a strided top pass whose rows are whole runs of coefficients: z <= nb and k >= lo of that pass
     if (m < 13 || np < 2 || z == 0 || z > nb[np - 1]) {
         for (uint32_t c = 0; c < ncols; c++) {
-            P_TRY(hipMemcpyAsync(out + ((size_t)c << m), coefs + ((size_t)c << k), (size_t)4 << k, hipMemcpyDeviceToDevice,
+            HIP_TRY(hipMemcpyAsync(out + ((size_t)c << m), coefs + ((size_t)c << k), (size_t)4 << k, hipMemcpyDeviceToDevice,
                                  (hipStream_t)stream));
-            if (z) P_TRY(hipMemsetAsync(out + ((size_t)c << m) + ((size_t)1 << k), 0, ((size_t)4 << m) - ((size_t)4 << k), (hipStream_t)stream));
+            if (z) HIP_TRY(hipMemsetAsync(out + ((size_t)c << m) + ((size_t)1 << k), 0, ((size_t)4 << m) - ((size_t)4 << k), (hipStream_t)stream));
         }
         return ss_p_fft(ctx, m, ncols, out, tw, 0, stream);
     }
@@ -1130,7 +873,7 @@ extern "C" int ss_p_lde(ss_ctx *ctx, uint32_t k, uint32_t m, uint32_t ncols, con
             launch_strided_pass(m, lo[i], nb[i], ncols, out, tw, 0, 1u, i == np - 1 ? coefs : nullptr, i == np - 1 ? z : 0u,
                                 (hipStream_t)stream);
     }
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1151,7 +894,7 @@ extern "C" int ss_p_hash_rows(ss_ctx *ctx, uint32_t hash, size_t n, uint32_t w, 
         else if (w == 16) launch(p_hash_rows_kernel<0, 16>);
         else launch(p_hash_rows_kernel<0, 0>);
     }
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1163,7 +906,7 @@ extern "C" int ss_p_hash_qm31(ss_ctx *ctx, uint32_t hash, size_t n, const uint32
         hipLaunchKernelGGL(p_hash_qm31_kernel<1>, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, n, vals, out);
     else
         hipLaunchKernelGGL(p_hash_qm31_kernel<0>, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, n, vals, out);
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1189,7 +932,7 @@ extern "C" int ss_p_merkle(ss_ctx *ctx, uint32_t hash, size_t n_leaves, uint32_t
                                parents, children, out);
         off += n;
     }
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1201,7 +944,7 @@ extern "C" int ss_p_merkle_dup(ss_ctx *ctx, uint32_t hash, size_t n, const uint3
         hipLaunchKernelGGL(p_merkle_dup_kernel<1>, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, n, leaf, out);
     else
         hipLaunchKernelGGL(p_merkle_dup_kernel<0>, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, n, leaf, out);
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1213,7 +956,7 @@ extern "C" int ss_p_composition(ss_ctx *ctx, uint32_t n_log, uint32_t n_cols, co
         return ss_internal_set_err(SS_ERR_ARG, "ss_p_composition: bad argument");
     hipLaunchKernelGGL(p_composition_kernel, dim3(blocks_for(1u << (n_log + 1))), dim3(256), 0, (hipStream_t)stream,
                        n_log, n_cols, ev, hx_c, q4(alpha), out);
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1225,7 +968,7 @@ extern "C" int ss_p_composition_dev(ss_ctx *ctx, uint32_t n_log, uint32_t n_cols
         return ss_internal_set_err(SS_ERR_ARG, "ss_p_composition_dev: bad argument");
     hipLaunchKernelGGL(p_composition_dev_kernel, dim3(blocks_for(1u << (n_log + 1))), dim3(256), 0, (hipStream_t)stream,
                        n_log, n_cols, ev, hx_c, alpha_dev, out);
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1248,7 +991,7 @@ extern "C" int ss_p_eval_at_point(ss_ctx *ctx, uint32_t m, const uint32_t *coeff
                            q4(factors_host + 4 * lvl), lvl + 1 == m ? out : dst);
         uint32_t *t = src; src = dst; dst = t;
     }
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1275,7 +1018,7 @@ extern "C" int ss_p_eval_at_point_batch(ss_ctx *ctx, uint32_t m, uint32_t ncols,
                            q4(factors_host + 4 * lvl), last ? out : dst, last ? (size_t)4 : sstride);
         uint32_t *t = src; src = dst; dst = t;
     }
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1291,7 +1034,7 @@ extern "C" int ss_p_channel_fri_layer(ss_ctx *ctx, uint32_t hash, uint32_t *stat
     else
         hipLaunchKernelGGL(p_channel_fri_layer_kernel<0>, dim3(1), dim3(64), 0, (hipStream_t)stream, state_dev, root_dev,
                            alpha_out_dev, root_out_dev);
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1303,7 +1046,7 @@ extern "C" int ss_p_fri_fold_dev(ss_ctx *ctx, size_t n_out, const uint32_t *in, 
         return ss_internal_set_err(SS_ERR_ARG, "ss_p_fri_fold_dev: bad argument");
     hipLaunchKernelGGL(p_fri_fold_dev_kernel, dim3(blocks_for(n_out)), dim3(256), 0, (hipStream_t)stream, n_out, in,
                        coord_inv, alpha_dev, out);
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1323,7 +1066,7 @@ extern "C" int ss_p_quotients(ss_ctx *ctx, uint32_t lde_log, uint32_t n_cols, co
     const size_t half = (size_t)1 << (lde_log - 1);
     hipLaunchKernelGGL(p_quotients_kernel, dim3(blocks_for(half)), dim3(256), 0, (hipStream_t)stream,
                        lde_log, n_cols, trace_lde, cp_lde, cp_log, hx_hy, hx_hy + half, bcoef, q, out);
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1338,7 +1081,7 @@ extern "C" int ss_p_quotients_dev(ss_ctx *ctx, uint32_t lde_log, uint32_t n_cols
     const size_t half = (size_t)1 << (lde_log - 1);
     hipLaunchKernelGGL(p_quotients_dev_kernel, dim3(blocks_for(half)), dim3(256), 0, (hipStream_t)stream,
                        lde_log, n_cols, trace_lde, cp_lde, cp_log, hx_hy, hx_hy + half, bcoef, points_dev, sums_alpha16_dev, out);
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1349,7 +1092,7 @@ extern "C" int ss_p_fri_fold(ss_ctx *ctx, size_t n_out, const uint32_t *in, cons
     if (!in || !coord_inv || !alpha || !out || !n_out) return ss_internal_set_err(SS_ERR_ARG, "ss_p_fri_fold: bad argument");
     hipLaunchKernelGGL(p_fri_fold_kernel, dim3(blocks_for(n_out)), dim3(256), 0, (hipStream_t)stream, n_out, in,
                        coord_inv, q4(alpha), out);
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1359,7 +1102,7 @@ extern "C" int ss_p_pow(ss_ctx *ctx, uint32_t hash, const uint32_t digest[8], ui
     SS_DEVICE_GUARD(ctx);
     if (!digest || !nonce_out_dev || !count || hash > 1) return ss_internal_set_err(SS_ERR_ARG, "ss_p_pow: bad argument");
     hipStream_t s = (hipStream_t)stream;
-    P_TRY(hipMemsetAsync(nonce_out_dev, 0xff, 8, s));
+    HIP_TRY(hipMemsetAsync(nonce_out_dev, 0xff, 8, s));
     Dig d;
     for (int i = 0; i < 8; i++) d.v[i] = hash ? __builtin_bswap32(digest[i]) : digest[i];
     if (hash)
@@ -1368,7 +1111,7 @@ extern "C" int ss_p_pow(ss_ctx *ctx, uint32_t hash, const uint32_t digest[8], ui
     else
         hipLaunchKernelGGL(p_pow_kernel<0>, dim3(blocks_for(count)), dim3(256), 0, s, d, target, start, count,
                            (unsigned long long *)nonce_out_dev);
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1387,7 +1130,7 @@ extern "C" int ss_p_finish_dev(ss_ctx *ctx, uint32_t hash, uint32_t lde_log, uin
     };
     if (hash) launch(p_finish_kernel<1>);
     else launch(p_finish_kernel<0>);
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -1408,6 +1151,6 @@ extern "C" int ss_p_decommit_record(ss_ctx *ctx, const ss_stwo_cfg *cfg, const s
     hipLaunchKernelGGL(p_decommit_record_kernel, dim3(blocks_for(chains, kDecommitChains) + 1), dim3(kDecommitThreads), 0,
                        (hipStream_t)stream, a, trees_dev, samples_dev, fri_roots_dev, last_dev, nonce_dev, queries_dev,
                        record_out_dev);
-    P_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }

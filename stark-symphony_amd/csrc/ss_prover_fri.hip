@@ -29,27 +29,13 @@
 // (v0 + v1) + alpha * ((v0 - v1) * coord_inv).  All of it is exact integer arithmetic on canonical words.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-
 #include "../../include/ss_prover.h"
-#include "ss_channel.h"
 #include "ss_ctx.h"
-#include "ss_fields.h"
-#include "ss_hash.h"
+#include "ss_prover_dev.h"
 
 using namespace ss;
 
 extern "C" int ss_internal_set_err(int code, const char *msg);
-
-#define PF_TRY(expr)                                                                 \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess) {                                                      \
-            char buf_[256];                                                          \
-            snprintf(buf_, sizeof buf_, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            return ss_internal_set_err(SS_ERR_HIP, buf_);                            \
-        }                                                                            \
-    } while (0)
 
 namespace ss {
 namespace {
@@ -66,37 +52,6 @@ constexpr uint32_t kPlaneB = kTailThreads / 2;  // ... and of the level after it
 static_assert((1u << kTailLog) == 4 * kTailThreads, "a thread owns at most two storage pairs");
 static_assert(8 * kPlaneB == 4 * kTailThreads, "the value tile shares the second node buffer");
 
-__device__ __forceinline__ QM31 ldq4(const uint32_t *p)
-{
-    const uint4 v = *reinterpret_cast<const uint4 *>(p);
-    return QM31{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ void stq4(uint32_t *p, QM31 v) { *reinterpret_cast<uint4 *>(p) = make_uint4(v.a, v.b, v.c, v.d); }
-
-// a node in the hash's native words -> row `row` of a tree, in stored words
-template <int HF>
-__device__ __forceinline__ void st_node(uint32_t *tree, uint32_t row, const uint32_t (&d)[8])
-{
-    uint4 *o = reinterpret_cast<uint4 *>(tree + (size_t)row * 8);
-    o[0] = make_uint4(Hasher<HF>::native(d[0]), Hasher<HF>::native(d[1]), Hasher<HF>::native(d[2]), Hasher<HF>::native(d[3]));
-    o[1] = make_uint4(Hasher<HF>::native(d[4]), Hasher<HF>::native(d[5]), Hasher<HF>::native(d[6]), Hasher<HF>::native(d[7]));
-}
-
-__device__ __forceinline__ QM31 fri_fold(QM31 v0, QM31 v1, uint32_t cinv, QM31 alpha)
-{
-    const QM31 f0 = qm31_add(v0, v1);
-    const QM31 f1 = qm31_mul_m31(qm31_sub(v0, v1), cinv);
-    return qm31_add(f0, qm31_mul(f1, alpha));
-}
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-
-__device__ __forceinline__ QM31 lane_q(QM31 v, uint32_t src)
-{
-    return QM31{(uint32_t)__shfl((int)v.a, (int)src), (uint32_t)__shfl((int)v.b, (int)src),
-                (uint32_t)__shfl((int)v.c, (int)src), (uint32_t)__shfl((int)v.d, (int)src)};
-}
-
 template <int HF>
 __global__ void __launch_bounds__(kTailThreads)
 p_fri_tail_kernel(uint32_t log_n, uint32_t n_layers, uint32_t *__restrict__ state, const uint32_t *__restrict__ layer,
@@ -112,9 +67,10 @@ p_fri_tail_kernel(uint32_t log_n, uint32_t n_layers, uint32_t *__restrict__ stat
     // The channel: the same in every lane of wavefront 0 (and unused in the others), so it is read through
     // readfirstlane and lives in scalar registers, native digest words + num_sent.
     Channel<HF> ch;
+    channel_load(ch, state);
 #pragma unroll
-    for (int i = 0; i < 8; i++) ch.dig.v[i] = Hasher<HF>::native(uni(state[i]));
-    ch.ctr = uni(state[8]);
+    for (int i = 0; i < 8; i++) ch.dig.v[i] = uni(ch.dig.v[i]);
+    ch.ctr = uni(ch.ctr);
 
     uint32_t n = 1u << log_n;
     // The thread's pair.  With two pairs a thread (layer 0 of a 2^kTailLog start) they are read where they are used,
@@ -171,11 +127,7 @@ p_fri_tail_kernel(uint32_t log_n, uint32_t n_layers, uint32_t *__restrict__ stat
             if (mix) {
 #pragma unroll
                 for (int k = 0; k < 8; k++) { l[k] = ch.dig.v[k]; r[k] = (uint32_t)__shfl((int)h[k], 0); }
-                if (t == 0) {
-                    uint4 *ro = reinterpret_cast<uint4 *>(roots_out + 8 * j);
-                    ro[0] = make_uint4(Hasher<HF>::native(r[0]), Hasher<HF>::native(r[1]), Hasher<HF>::native(r[2]), Hasher<HF>::native(r[3]));
-                    ro[1] = make_uint4(Hasher<HF>::native(r[4]), Hasher<HF>::native(r[5]), Hasher<HF>::native(r[6]), Hasher<HF>::native(r[7]));
-                }
+                if (t == 0) st_node<HF>(roots_out, j, r);
             } else if (have_lr) {
 #pragma unroll
                 for (int k = 0; k < 8; k++) { l[k] = h[k]; r[k] = hr[k]; }
@@ -283,11 +235,7 @@ p_fri_tail_kernel(uint32_t log_n, uint32_t n_layers, uint32_t *__restrict__ stat
         n = np;
     }
 
-    if (t == 0) {
-#pragma unroll
-        for (int i = 0; i < 8; i++) state[i] = Hasher<HF>::native(ch.dig.v[i]);
-        state[8] = ch.ctr;
-    }
+    if (t == 0) channel_store(ch, state);
 }
 
 }  // namespace
@@ -321,6 +269,6 @@ extern "C" int ss_p_fri_tail_dev(ss_ctx *ctx, uint32_t hash, uint32_t log_n, uin
     else
         hipLaunchKernelGGL(p_fri_tail_kernel<0>, dim3(1), dim3(threads), 0, (hipStream_t)stream, log_n, n_layers, state_dev,
                            layer_dev, coord_inv_dev, arena_dev, roots_out_dev, alphas_out_dev);
-    PF_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }

@@ -19,26 +19,14 @@
 // the lanes striding over the columns.  One more workgroup writes the head, the list lengths and the size.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-
 #include "../../include/ss_prover.h"
 #include "ss_ctx.h"
-#include "ss_layout.h"
 #include "ss_minimal.h"
+#include "ss_prover_dev.h"
 
 using namespace ss;
 
 extern "C" int ss_internal_set_err(int code, const char *msg);
-
-#define PM_TRY(expr)                                                                 \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess) {                                                      \
-            char buf_[256];                                                          \
-            snprintf(buf_, sizeof buf_, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            return ss_internal_set_err(SS_ERR_HIP, buf_);                            \
-        }                                                                            \
-    } while (0)
 
 namespace ss {
 namespace {
@@ -61,16 +49,6 @@ struct MinPlanDev {
     uint32_t base[kMinLists];    // first word of each of those lists
     uint32_t n_vals, words;      // |Nodes(0)|; the record's size
 };
-
-__device__ __forceinline__ void move16(uint32_t *dst, const uint32_t *src)
-{
-    const uint4 v = *reinterpret_cast<const uint4 *>(src);
-    if (((uintptr_t)dst & 15) == 0) {
-        *reinterpret_cast<uint4 *>(dst) = v;
-    } else {
-        dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
-    }
-}
 
 __device__ __forceinline__ uint32_t wave_scan(uint32_t v, uint32_t lane)  // inclusive
 {
@@ -303,7 +281,7 @@ extern "C" int ss_p_decommit_minimal(ss_ctx *ctx, const ss_stwo_cfg *cfg, const 
     hipLaunchKernelGGL(p_decommit_minimal_kernel, dim3((items + kMinWaves - 1) / kMinWaves + 1), dim3(kMinThreads), 0,
                        (hipStream_t)stream, a, trees_dev, samples_dev, fri_roots_dev, last_dev, nonce_dev, queries_dev,
                        minimal_out_dev, words_out_dev);
-    PM_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -316,12 +294,12 @@ extern "C" int ss_p_minimal_pack_dev(ss_ctx *ctx, size_t n, const uint32_t *rows
         return ss_internal_set_err(SS_ERR_ARG, "ss_p_minimal_pack_dev: bad argument");
     hipLaunchKernelGGL(p_minimal_offs_kernel, dim3(1), dim3(kPackThreads), 0, (hipStream_t)stream, n, words_dev,
                        (uint32_t)row_stride_words, offs_out_dev);
-    PM_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     if (!n) return SS_OK;
     // four words per thread and pass at the longest record; the y dimension loops past its limit
     const dim3 grid((unsigned)((row_stride_words + 4 * kPackThreads - 1) / (4 * kPackThreads)), (unsigned)(n < 65535 ? n : 65535));
     hipLaunchKernelGGL(p_minimal_pack_kernel, grid, dim3(kPackThreads), 0, (hipStream_t)stream, n, rows_dev, row_stride_words,
                        offs_out_dev, packed_out_dev);
-    PM_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }

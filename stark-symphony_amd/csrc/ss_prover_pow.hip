@@ -38,13 +38,9 @@
 // midstate (the nonce enters round 0 already); it calls Hasher<1>::block itself with the digest in scalar registers.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-
 #include "../../include/ss_prover.h"
-#include "ss_channel.h"
 #include "ss_ctx.h"
-#include "ss_hash.h"
-#include "ss_layout.h"
+#include "ss_prover_dev.h"
 
 using namespace ss;
 
@@ -63,8 +59,6 @@ static_assert((kChunk & (kChunk - 1)) == 0 && kChunk <= ((uint64_t)1 << 32), "a 
 // Workgroups per compute unit: four wavefronts per SIMD, which the SHA-256 variant's 108 VGPRs just allow.  Two are
 // within the spread up to 2^26 nonces and 9 % slower at 2^28 (32.96 against 36.05 G/s); one loses 20 %.
 constexpr uint32_t kGridPerCu = 4;
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
 template <int HF>
 struct PowHash;
@@ -205,19 +199,12 @@ p_finish_grid_kernel(uint32_t *__restrict__ state, const uint32_t *__restrict__ 
     constexpr unsigned long long kNone = ~0ull;
     unsigned long long *claim_w = work, *best_w = work + 1, *gone_w = work + 2;  // best_w holds ~best
     const uint32_t tid = threadIdx.x;
-    const uint4 *rows = reinterpret_cast<const uint4 *>(last);
-    const uint4 first = rows[0];
-    int differs = 0;
-    for (size_t i = tid; i < n_last; i += kPowThreads) {
-        const uint4 v = rows[i];
-        differs |= (v.x != first.x) | (v.y != first.y) | (v.z != first.z) | (v.w != first.w);
-    }
+    const int differs = last_layer_differs(last, n_last, tid, kPowThreads);
+    const QM31 first = ldq4(last);
     Channel<HF> ch;
-#pragma unroll
-    for (int i = 0; i < 8; i++) ch.dig.v[i] = Hasher<HF>::native(state[i]);
-    ch.ctr = state[8];
+    channel_load(ch, state);
     const int bad_layer = __syncthreads_or(differs);
-    const uint32_t lv[4] = {first.x, first.y, first.z, first.w};
+    const uint32_t lv[4] = {first.a, first.b, first.c, first.d};
     mix_values<HF>(ch, lv);
     PowHash<HF> ph;
     ph.init(ch.dig.v);
@@ -270,24 +257,9 @@ p_finish_grid_kernel(uint32_t *__restrict__ state, const uint32_t *__restrict__ 
     if (nonce != kNone) {
         const uint32_t nv[2] = {(uint32_t)(nonce >> 32), (uint32_t)nonce};
         mix_values<HF>(ch, nv);
-        const uint32_t mask = (uint32_t)(((uint64_t)1 << lde_log) - 1);
-        for (uint32_t got = 0; got < n_queries; got += 8) {
-            const uint32_t m[1] = {ch.ctr};
-            uint32_t w[8];
-            Hasher<HF>::template block<true, 8, 1>(ch.dig.v, m, w);  // Channel<HF>::draw_words
-            ch.ctr = ch.ctr + 1;
-#pragma unroll
-            for (int i = 0; i < 8; i++) w[i] = Hasher<HF>::native(w[i]);
-            if (tid == 0) {
-#pragma unroll
-                for (uint32_t k = 0; k < 8; k++)
-                    if (got + k < n_queries) queries[got + k] = w[k] & mask;
-            }
-        }
+        draw_queries<HF, true>(ch, lde_log, n_queries, tid == 0, queries);  // (inlined, as mix_values above)
         if (tid == 0) {
-#pragma unroll
-            for (int i = 0; i < 8; i++) state[i] = Hasher<HF>::native(ch.dig.v[i]);
-            state[8] = ch.ctr;
+            channel_store(ch, state);
             nonce_out[0] = nv[0];
             nonce_out[1] = nv[1];
         }
@@ -325,11 +297,6 @@ extern "C" int ss_p_finish_grid_dev(ss_ctx *ctx, uint32_t hash, uint32_t lde_log
     };
     if (hash) launch(p_finish_grid_kernel<1>);
     else launch(p_finish_grid_kernel<0>);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char buf[256];
-        snprintf(buf, sizeof buf, "ss_p_finish_grid_dev: launch failed: %s", hipGetErrorString(e));
-        return ss_internal_set_err(SS_ERR_HIP, buf);
-    }
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }

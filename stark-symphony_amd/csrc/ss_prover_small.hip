@@ -24,32 +24,18 @@
 //   hashing    the pair hash is ONE out-of-line copy (node_call), the leaf / channel / nonce hashes go through the
 //              out-of-line compressions of ss_hash.h: inlining one per phase is 15 copies of 64 unrolled rounds.
 //
-// The arithmetic is the device functions of ss_fields.h / ss_hash.h / ss_channel.h on canonical words, phase by phase
-// the expressions of the kernels in ss_prover.hip and ss_prover_transcript.hip: the same bits.
+// What a phase computes is not written here: every phase calls the step of ss_prover_dev.h that the kernels of
+// ss_prover.hip and ss_prover_transcript.hip call for the same element, with the variable of its workgroup-stride loop
+// as the index.  This file holds where the operands live and who waits for whom.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-
 #include "../../include/ss_prover.h"
-#include "ss_channel.h"
 #include "ss_ctx.h"
-#include "ss_fields.h"
-#include "ss_hash.h"
-#include "ss_layout.h"
+#include "ss_prover_dev.h"
 
 using namespace ss;
 
 extern "C" int ss_internal_set_err(int code, const char *msg);
-
-#define PS_TRY(expr)                                                                 \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess) {                                                      \
-            char buf_[256];                                                          \
-            snprintf(buf_, sizeof buf_, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            return ss_internal_set_err(SS_ERR_HIP, buf_);                            \
-        }                                                                            \
-    } while (0)
 
 namespace ss {
 namespace {
@@ -97,36 +83,15 @@ struct SmallArgs {
 
 // what the phases hand each other besides the arena
 struct SmallShared {
+    alignas(16) uint32_t samples[4 * kMaxSamples];
+    alignas(16) uint32_t bcoef[4 * kMaxSamples];  // (quotients_pair reads a column's coefficient as one uint4)
     uint32_t cp_alpha[4], points[16], sums[20], alpha[4], last[4], nonce[2], dig[8];
     uint32_t f1[4 * kMaxTraceLog], f2x[4 * kMaxTraceLog];
-    uint32_t samples[4 * kMaxSamples], bcoef[4 * kMaxSamples];
     uint32_t troot[8], croot[8], roots[8 * kMaxTraceLog];  // stored words
     uint32_t queries[kSmallQueries];
     unsigned long long best;
     QM31 wave[2][kWaves];
 };
-
-__device__ __forceinline__ QM31 ldq(const uint32_t *p) { return QM31{p[0], p[1], p[2], p[3]}; }
-__device__ __forceinline__ void stq(uint32_t *p, QM31 v) { p[0] = v.a; p[1] = v.b; p[2] = v.c; p[3] = v.d; }
-__device__ __forceinline__ QM31 ldq4(const uint32_t *p)
-{
-    const uint4 v = *reinterpret_cast<const uint4 *>(p);
-    return QM31{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ void stq4(uint32_t *p, QM31 v) { *reinterpret_cast<uint4 *>(p) = make_uint4(v.a, v.b, v.c, v.d); }
-__device__ __forceinline__ QM31 qm31_add_c(QM31 x, QM31 y)
-{
-    return {m31_add_c(x.a, y.a), m31_add_c(x.b, y.b), m31_add_c(x.c, y.c), m31_add_c(x.d, y.d)};
-}
-__device__ __forceinline__ QM31 q_shfl_down(QM31 v, uint32_t d)
-{
-    return {__shfl_down(v.a, d, 64), __shfl_down(v.b, d, 64), __shfl_down(v.c, d, 64), __shfl_down(v.d, d, 64)};
-}
-__device__ __forceinline__ QM31 q_shfl_up(QM31 v, uint32_t d)
-{
-    return {__shfl_up(v.a, d, 64), __shfl_up(v.b, d, 64), __shfl_up(v.c, d, 64), __shfl_up(v.d, d, 64)};
-}
-__device__ __forceinline__ QM31 fold_q(QM31 even, QM31 odd, QM31 f) { return qm31_add_c(even, qm31_mul_c(odd, f)); }
 
 // ------------------------------------------------------------------------------ hashing
 template <int HF>
@@ -135,23 +100,6 @@ __device__ __noinline__ Dig node_call(Dig l, Dig r)
     Dig d;
     Hasher<HF>::template pair<true>(l.v, r.v, d.v);
     return d;
-}
-
-// a node in the hash's native words -> row `row` of a tree, in stored words
-template <int HF>
-__device__ __forceinline__ void st_node(uint32_t *tree, uint32_t row, const uint32_t (&d)[8])
-{
-    uint4 *o = reinterpret_cast<uint4 *>(tree + (size_t)row * 8);
-    o[0] = make_uint4(Hasher<HF>::native(d[0]), Hasher<HF>::native(d[1]), Hasher<HF>::native(d[2]), Hasher<HF>::native(d[3]));
-    o[1] = make_uint4(Hasher<HF>::native(d[4]), Hasher<HF>::native(d[5]), Hasher<HF>::native(d[6]), Hasher<HF>::native(d[7]));
-}
-template <int HF>
-__device__ __forceinline__ Dig ld_node(const uint32_t *tree, uint32_t row)
-{
-    const uint4 *c = reinterpret_cast<const uint4 *>(tree + (size_t)row * 8);
-    const uint4 a = c[0], b = c[1];
-    return Dig{{Hasher<HF>::native(a.x), Hasher<HF>::native(a.y), Hasher<HF>::native(a.z), Hasher<HF>::native(a.w),
-                Hasher<HF>::native(b.x), Hasher<HF>::native(b.y), Hasher<HF>::native(b.z), Hasher<HF>::native(b.w)}};
 }
 
 // The tree over n = 2^k >= 2 leaves into tree[2n][8] (ss_p_merkle's layout: leaves first, root in row 2n - 2).
@@ -297,49 +245,6 @@ __device__ __forceinline__ void lde_column(uint32_t *buf, const uint32_t *src, u
     __syncthreads();
 }
 
-// ------------------------------------------------------------------------------ channel pieces
-// digest <- H(digest || words[0 .. count)) for a message of any length (channel_mix_oods_evals), then num_sent = 0
-template <int HF>
-__device__ __forceinline__ void mix_stream(Channel<HF> &ch, const uint32_t *words, uint32_t count)
-{
-    const uint32_t total = 8 + count, nblk = Hasher<HF>::n_blocks(total);
-    Dig st;
-    Hasher<HF>::iv(st.v);
-    for (uint32_t blk = 0; blk < nblk; blk++) {
-        W16 w;
-        Hasher<HF>::fill(w, blk, nblk, total, ch.dig.v, [&](int, uint32_t i) { return words[i]; });
-        if (HF) {
-            const bool last = blk + 1 == nblk;
-            st = b2s_compress_call(st, w, last ? 4u * total : 64u * (blk + 1), last);
-        } else {
-            st = sha_compress_call(st, w);
-        }
-    }
-    ch.dig = st;
-    ch.ctr = 0;
-}
-
-// deep/quotients.simf:25-36 on canonical values: a0 = -2 Im(v) u, b0 = -2 Im(y) u, c0 = b0 v - a0 y, times alpha^i
-__device__ __forceinline__ void deep_interpolant(QM31 sp_y, QM31 v, QM31 alpha_i, QM31 &a, QM31 &b, QM31 &c)
-{
-    auto neg2 = [](uint32_t x) { return m31_sub_c(0, m31_add_c(x, x)); };
-    const CM31 a0 = {neg2(v.c), neg2(v.d)}, b0 = {neg2(sp_y.c), neg2(sp_y.d)};
-    const QM31 c0 = qm31_sub(qm31_mul_im_c(v, b0), qm31_mul_im_c(sp_y, a0));
-    a = qm31_mul_im_c(alpha_i, a0);
-    b = qm31_mul_im_c(alpha_i, b0);
-    c = qm31_mul_c(alpha_i, c0);
-}
-
-__device__ __forceinline__ void move16(uint32_t *dst, const uint32_t *src)
-{
-    const uint4 v = *reinterpret_cast<const uint4 *>(src);
-    if (((uintptr_t)dst & 15) == 0) {
-        *reinterpret_cast<uint4 *>(dst) = v;
-    } else {
-        dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
-    }
-}
-
 // ------------------------------------------------------------------------------ the kernel
 template <int HF>
 __global__ void __launch_bounds__(kNT) p_prove_small_kernel(SmallArgs A)
@@ -363,20 +268,10 @@ __global__ void __launch_bounds__(kNT) p_prove_small_kernel(SmallArgs A)
         Channel<HF> ch;  // wavefront 0 only
         uint32_t errbits = 0;
 
-        // ---- trace (p_trace_kernel): row r = 1, r + seed term, c_k = c_{k-1}^2 + c_{k-2}^2
+        // ---- trace
         {
             const uint32_t seed_term = (uint32_t)(((A.seeds[proof] % M31_P) * (0x9E3779B1ull % M31_P)) % M31_P);
-            for (uint32_t r = t; r < rows; r += kNT) {
-                uint32_t a = 1, b = m31_add(m31_red(r), seed_term);
-                coefs[r] = a;
-                if (N > 1) coefs[rows + r] = b;
-                for (uint32_t k = 2; k < N; k++) {
-                    const uint32_t c = m31_add(m31_sqr(b), m31_sqr(a));
-                    coefs[k * rows + r] = c;
-                    a = b;
-                    b = c;
-                }
-            }
+            for (uint32_t r = t; r < rows; r += kNT) trace_row(r, seed_term, N, rows, coefs);
         }
         __syncthreads();
 
@@ -429,29 +324,10 @@ __global__ void __launch_bounds__(kNT) p_prove_small_kernel(SmallArgs A)
         }
         __syncthreads();
 
-        // ---- composition polynomial on the coset of log size n + 1 (composition_row)
+        // ---- composition polynomial on the coset of log size n + 1
         {
             const QM31 alpha = ldq(S.cp_alpha);
-            for (uint32_t i = t; i < csize; i += kNT) {
-                uint32_t van = A.tb.hxhy_c[i >> 1];
-                for (uint32_t k = 1; k < n; k++) van = m31_dbl_x(van);
-                uint32_t van_inv;
-                m31_inv(van, van_inv);
-                QM31 acc = qm31_zero();
-                uint32_t a = ev[i], b = N > 1 ? ev[csize + i] : 0;
-                for (uint32_t k = 2; k < N; k++) {
-                    const uint32_t c = ev[k * csize + i];
-                    const uint32_t cons = m31_sub(c, m31_add(m31_sqr(b), m31_sqr(a)));
-                    acc = qm31_mul(acc, alpha);
-                    acc.a = m31_add(acc.a, cons);
-                    a = b;
-                    b = c;
-                }
-                F[i] = m31_mul(acc.a, van_inv);
-                F[csize + i] = m31_mul(acc.b, van_inv);
-                F[2 * csize + i] = m31_mul(acc.c, van_inv);
-                F[3 * csize + i] = m31_mul(acc.d, van_inv);
-            }
+            for (uint32_t i = t; i < csize; i += kNT) composition_point(i, n, N, ev, A.tb.hxhy_c, alpha, F);
             __syncthreads();
             // its iFFT; coefficient j of coordinate c goes to partition 4 c + (j & 3), place j >> 2
             const uint32_t scale = (1u << ((31 - ((n + 1) % 31)) % 31)) % M31_P;
@@ -485,23 +361,10 @@ __global__ void __launch_bounds__(kNT) p_prove_small_kernel(SmallArgs A)
                 uint32_t r[8];
 #pragma unroll
                 for (int k = 0; k < 8; k++) r[k] = Hasher<HF>::native(root.v[k]);
-                ch.mix(r);
-                QM31 tq, inv;
-                bool ok = ch.draw_qm31(tq);
-                const QM31 t_sq = qm31_mul(tq, tq);
-                ok &= qm31_inv(qm31_add(qm31_one(), t_sq), inv);
-                if (!ok) errbits |= SS_P_ERR_TRANSCRIPT;
-                const QM31 px = qm31_mul(qm31_sub(qm31_one(), t_sq), inv), py = qm31_mul(qm31_add(tq, tq), inv);
-                const QM31 p2x = qm31_dbl_x(px), pxy = qm31_mul(px, py), p2y = qm31_add(pxy, pxy);
+                if (!oods_point<HF>(ch, r, n, t == 0, S.points, S.f1, S.f2x)) errbits |= SS_P_ERR_TRANSCRIPT;
                 if (t == 0) {
 #pragma unroll
                     for (int k = 0; k < 8; k++) S.croot[k] = r[k];
-                    stq(S.points, px); stq(S.points + 4, py); stq(S.points + 8, p2x); stq(S.points + 12, p2y);
-                    stq(S.f1, py);
-                    QM31 cur = px;
-                    for (uint32_t i = 1; i < n; i++) { stq(S.f1 + 4 * i, cur); cur = qm31_dbl_x(cur); }
-                    cur = p2x;
-                    for (uint32_t i = 0; i + 1 < n; i++) { stq(S.f2x + 4 * i, cur); cur = qm31_dbl_x(cur); }
                 }
             }
         }
@@ -519,42 +382,15 @@ __global__ void __launch_bounds__(kNT) p_prove_small_kernel(SmallArgs A)
                 const uint32_t *fac = tr ? S.f1 : S.f2x;
                 QM31 r = qm31_zero();
                 if (live) {
-                    const QM31 f0 = ldq(fac);
                     uint32_t cf[16];
 #pragma unroll
                     for (uint32_t k = 0; k < 16; k++) cf[k] = e0 + k < n_tile ? src[k] : 0u;
-                    QM31 v[8];
-#pragma unroll
-                    for (uint32_t j = 0; j < 8; j++) {
-                        const uint32_t o = cf[2 * j + 1];
-                        v[j] = QM31{m31_add_c(m31_mul_c(f0.a, o), cf[2 * j]), m31_mul_c(f0.b, o), m31_mul_c(f0.c, o), m31_mul_c(f0.d, o)};
-                    }
-#pragma unroll
-                    for (uint32_t s = 1; s < 4; s++) {
-                        if (s < lv) {
-                            const QM31 f = ldq(fac + 4 * s);
-#pragma unroll
-                            for (uint32_t j = 0; j < (8u >> s); j++) v[j] = fold_q(v[2 * j], v[2 * j + 1], f);
-                        }
-                    }
-                    r = v[0];
+                    r = eval_fold16(cf, fac, lv);
                 }
-#pragma unroll
-                for (uint32_t s = 0; s < 6; s++) {  // (whole wavefronts: a group is four of them)
-                    const QM31 up = q_shfl_down(r, 1u << s);
-                    if (live && 4 + s < lv) r = fold_q(r, up, ldq(fac + 4 * (4 + s)));
-                }
+                r = eval_fold_wave(r, fac, live ? lv : 0u);  // (whole wavefronts: a group is four of them)
                 if (lane == 0) S.wave[it & 1][wave] = r;
                 __syncthreads();
-                if (live && tid == 0) {
-                    const QM31 *w = &S.wave[it & 1][4 * grp];
-                    if (lv > 10) {
-                        const QM31 f10 = ldq(fac + 40);
-                        r = fold_q(r, w[1], f10);
-                        if (lv > 11) r = fold_q(r, fold_q(w[2], w[3], f10), ldq(fac + 44));
-                    }
-                    stq(S.samples + 4 * c, r);
-                }
+                if (live && tid == 0) stq(S.samples + 4 * c, eval_fold_waves(r, &S.wave[it & 1][4 * grp], fac, lv));
             }
             if (n == 1 && t < kCp) stq(S.samples + 4 * (N + t), QM31{cp_coefs[t], 0, 0, 0});  // every partition is a constant
         }
@@ -562,14 +398,10 @@ __global__ void __launch_bounds__(kNT) p_prove_small_kernel(SmallArgs A)
 
         // ---- deep_alpha and the DEEP coefficients (p_deep_coeffs_kernel), wavefront 0: N + 16 <= 48 columns, a lane each
         if (wave == 0) {
-            mix_stream<HF>(ch, S.samples, 4 * (N + kCp));
+            mix_stream<HF>(ch, S.samples, 4 * (N + kCp), CompressCall<HF>());
             QM31 pw;
             if (!ch.draw_qm31(pw)) errbits |= SS_P_ERR_TRANSCRIPT;
-#pragma unroll
-            for (uint32_t d = 1; d < 64; d <<= 1) {  // pw = alpha^(lane + 1)
-                const QM31 below = q_shfl_up(pw, d);
-                if (lane >= d) pw = qm31_mul_c(pw, below);
-            }
+            pw = alpha_powers(pw, lane);
             const QM31 py = ldq(S.points + 4), p2y = ldq(S.points + 12);
             auto batch = [&](bool mine, QM31 sp_y, uint32_t k, uint32_t *sums_out) {
                 QM31 a = qm31_zero(), b = a, c = a;
@@ -577,11 +409,7 @@ __global__ void __launch_bounds__(kNT) p_prove_small_kernel(SmallArgs A)
                     deep_interpolant(sp_y, ldq(S.samples + 4 * k), pw, a, b, c);
                     stq(S.bcoef + 4 * k, b);
                 }
-#pragma unroll
-                for (uint32_t d = 32; d; d >>= 1) {
-                    a = qm31_add_c(a, q_shfl_down(a, d));
-                    c = qm31_add_c(c, q_shfl_down(c, d));
-                }
+                wave_sum2(a, c);
                 if (lane == 0) { stq(sums_out, a); stq(sums_out + 4, c); }
             };
             batch(lane < N, py, lane, S.sums);
@@ -590,80 +418,11 @@ __global__ void __launch_bounds__(kNT) p_prove_small_kernel(SmallArgs A)
         }
         __syncthreads();
 
-        // ---- quotients (quotients_pair): a thread = a storage pair
+        // ---- quotients: a thread = a storage pair; the composition columns hold one value per pair (log size L - 1)
         {
-            const QM31 px = ldq(S.points), py = ldq(S.points + 4), p2x = ldq(S.points + 8), p2y = ldq(S.points + 12);
-            const QM31 a1 = ldq(S.sums), c1 = ldq(S.sums + 4), a2 = ldq(S.sums + 8), c2 = ldq(S.sums + 12), alpha16 = ldq(S.sums + 16);
-            uint32_t *out = layer_at(0);
-            for (uint32_t h = t; h < half; h += kNT) {
-                const uint32_t x = A.tb.hxhy_l[h], y0 = A.tb.hxhy_l[half + h];
-                const uint32_t ys[2] = {y0, m31_sub_c(0, y0)};
-                uint64_t acc[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-                uint32_t open = 0;
-                for (uint32_t k = 0; k < N; k++) {
-                    const uint2 v = *reinterpret_cast<const uint2 *>(lde + k * size + 2 * h);
-                    const QM31 c = ldq(S.bcoef + 4 * k);
-                    acc[0][0] = m31_mac(acc[0][0], c.a, v.x); acc[0][1] = m31_mac(acc[0][1], c.b, v.x);
-                    acc[0][2] = m31_mac(acc[0][2], c.c, v.x); acc[0][3] = m31_mac(acc[0][3], c.d, v.x);
-                    acc[1][0] = m31_mac(acc[1][0], c.a, v.y); acc[1][1] = m31_mac(acc[1][1], c.b, v.y);
-                    acc[1][2] = m31_mac(acc[1][2], c.c, v.y); acc[1][3] = m31_mac(acc[1][3], c.d, v.y);
-                    if (++open == 3) {
-#pragma unroll
-                        for (int p = 0; p < 2; p++)
-#pragma unroll
-                            for (int w = 0; w < 4; w++) acc[p][w] = m31_fold62(acc[p][w]);
-                        open = 0;
-                    }
-                }
-                QM31 s1[2];
-#pragma unroll
-                for (int p = 0; p < 2; p++)
-                    s1[p] = QM31{m31_red64(acc[p][0]), m31_red64(acc[p][1]), m31_red64(acc[p][2]), m31_red64(acc[p][3])};
-                uint64_t bc[4] = {0, 0, 0, 0};
-                open = 0;
-                for (uint32_t k = 0; k < kCp; k++) {  // (one value per pair)
-                    const uint32_t v = cp_lde[k * half + h];
-                    const QM31 c = ldq(S.bcoef + 4 * (N + k));
-                    bc[0] = m31_mac(bc[0], c.a, v); bc[1] = m31_mac(bc[1], c.b, v);
-                    bc[2] = m31_mac(bc[2], c.c, v); bc[3] = m31_mac(bc[3], c.d, v);
-                    if (++open == 3) {
-#pragma unroll
-                        for (int w = 0; w < 4; w++) bc[w] = m31_fold62(bc[w]);
-                        open = 0;
-                    }
-                }
-                const QM31 s2 = QM31{m31_red64(bc[0]), m31_red64(bc[1]), m31_red64(bc[2]), m31_red64(bc[3])};
-                // the four DEEP denominators (P, 2P) x (y, -y) share one M31 inversion
-                CM31 d[4];
-                uint32_t nrm[4], pre[4], run = 1;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const QM31 sx = j < 2 ? px : p2x, sy = j < 2 ? py : p2y;
-                    const CM31 dx = cm31_sub_m31(q_re(sx), x), dy = cm31_sub_m31(q_re(sy), ys[j & 1]);
-                    d[j] = cm31_sub(cm31_mul(dx, q_im(sy)), cm31_mul(dy, q_im(sx)));
-                    nrm[j] = m31_add(m31_sqr(d[j].a), m31_sqr(d[j].b));
-                    pre[j] = run;
-                    run = m31_mul(run, nrm[j] ? nrm[j] : 1u);
-                }
-                uint32_t inv;
-                m31_inv(run, inv);
-                CM31 dinv[4];
-#pragma unroll
-                for (int j = 3; j >= 0; j--) {
-                    const uint32_t ni = nrm[j] ? m31_mul(inv, pre[j]) : 0u;
-                    inv = m31_mul(inv, nrm[j] ? nrm[j] : 1u);
-                    dinv[j] = cm31_mul_m31(CM31{d[j].a, m31_neg(d[j].b)}, ni);
-                }
-                const QM31 a1y = qm31_mul_m31(a1, y0), a2y = qm31_mul_m31(a2, y0);
-#pragma unroll
-                for (int p = 0; p < 2; p++) {
-                    const QM31 t1 = p ? qm31_sub(c1, a1y) : qm31_add(a1y, c1);
-                    const QM31 t2 = p ? qm31_sub(c2, a2y) : qm31_add(a2y, c2);
-                    const QM31 b1 = qm31_mul_cm31(qm31_sub(s1[p], t1), dinv[p]);
-                    const QM31 b2 = qm31_mul_cm31(qm31_sub(s2, t2), dinv[2 + p]);
-                    stq4(out + 4 * (2 * h + p), qm31_add(qm31_mul(b1, alpha16), b2));
-                }
-            }
+            const QuotArgs qa = quot_args(S.points, S.sums);
+            for (uint32_t h = t; h < half; h += kNT)
+                quotients_pair(h, L, N, lde, cp_lde, L - 1, A.tb.hxhy_l, A.tb.hxhy_l + half, S.bcoef, qa, layer_at(0));
         }
         __syncthreads();
 
@@ -695,23 +454,17 @@ __global__ void __launch_bounds__(kNT) p_prove_small_kernel(SmallArgs A)
             const QM31 alpha = ldq(S.alpha);
             const uint32_t *cinv = A.tb.itw_l + (size - ln);  // inverse twiddle layer l = 1 / fold coordinate
             uint32_t *nxt = layer_at(l + 1);
-            for (uint32_t i = t; i < (ln >> 1); i += kNT) {
-                const QM31 v0 = ldq4(cur + 8 * i), v1 = ldq4(cur + 8 * i + 4);
-                const QM31 f0 = qm31_add(v0, v1);
-                const QM31 f1 = qm31_mul_m31(qm31_sub(v0, v1), cinv[i]);
-                stq4(nxt + 4 * i, qm31_add(f0, qm31_mul(f1, alpha)));
-            }
+            for (uint32_t i = t; i < (ln >> 1); i += kNT)
+                stq4(nxt + 4 * i, fri_fold(ldq4(cur + 8 * i), ldq4(cur + 8 * i + 4), cinv[i], alpha));
             __syncthreads();
         }
 
-        // ---- the transcript's tail (p_finish_kernel): last layer, proof of work, queries
+        // ---- the transcript's tail: last layer, proof of work, queries
         {
             const uint32_t *last = layer_at(K + 1);
-            const uint32_t n_last = size >> (K + 1);
-            const QM31 first = ldq4(last);
-            int differs = 0;
-            for (uint32_t i = t; i < n_last; i += kNT) differs |= !qm31_eq(ldq4(last + 4 * i), first);
+            const int differs = last_layer_differs(last, size >> (K + 1), t, kNT);
             if (wave == 0) {
+                const QM31 first = ldq4(last);
                 const uint32_t lv[4] = {first.a, first.b, first.c, first.d};
                 ch.mix_values(lv);
                 if (t == 0) {
@@ -725,35 +478,13 @@ __global__ void __launch_bounds__(kNT) p_prove_small_kernel(SmallArgs A)
             uint32_t dig[8];
 #pragma unroll
             for (int k = 0; k < 8; k++) dig[k] = S.dig[k];
-            unsigned long long nonce = ~0ull;
-            for (uint64_t base = 0; base < A.span; base += kNT) {
-                const uint64_t cand = base + t;
-                if (cand < A.span) {
-                    const uint32_t m[2] = {(uint32_t)(cand >> 32), (uint32_t)cand};
-                    uint32_t d[8];
-                    Hasher<HF>::template block<false, 8, 2>(dig, m, d);
-                    if (Hasher<HF>::pow_value(d) < A.target) atomicMin(&S.best, (unsigned long long)cand);
-                }
-                __syncthreads();
-                nonce = S.best;
-                __syncthreads();  // (nobody enters the next round's atomicMin before everybody has read this round's result)
-                if (nonce != ~0ull) break;
-            }
+            const unsigned long long nonce = pow_search_workgroup<HF, false>(dig, A.target, A.span, &S.best, t, kNT);
             if (nonce == ~0ull) errbits |= SS_P_ERR_POW_SPAN;
             if (wave == 0) {
-                const uint32_t mask = (1u << L) - 1;
                 if (nonce != ~0ull) {
                     const uint32_t nv[2] = {(uint32_t)(nonce >> 32), (uint32_t)nonce};
                     ch.mix_values(nv);
-                    for (uint32_t got = 0; got < Q; got += 8) {
-                        uint32_t w[8];
-                        ch.draw_words(w);
-                        if (t == 0) {
-#pragma unroll
-                            for (uint32_t k = 0; k < 8; k++)
-                                if (got + k < Q) S.queries[got + k] = w[k] & mask;
-                        }
-                    }
+                    draw_queries<HF, false>(ch, L, Q, t == 0, S.queries);
                     if (t == 0) { S.nonce[0] = nv[0]; S.nonce[1] = nv[1]; }
                 } else {
                     if (t < Q) S.queries[t] = 0;  // (the row's content is unspecified; its gather stays inside the slot)
@@ -764,30 +495,15 @@ __global__ void __launch_bounds__(kNT) p_prove_small_kernel(SmallArgs A)
         }
         __syncthreads();
 
-        // ---- decommitment into the row (p_decommit_record_kernel): a wavefront per chain, all threads for head and trailer
+        // ---- decommitment into the row: a wavefront per chain, all threads for head and trailer
         {
-            const uint32_t kinds = K + 3, oods = 4 * (N + kCp), head = 24 + oods + 8 * (K + 1) + 6, per_q = N + kCp + 16 * L;
-            for (uint32_t w = t; w < head; w += kNT) {
-                uint32_t v, r = w;
-                if (r < 8) {
-                    v = 0;
-#pragma unroll
-                    for (uint32_t k = 0; k < 8; k++)  // (a kernel argument: selected, not indexed)
-                        if (r == k) v = A.const_root.v[k];
-                }
-                else if ((r -= 8) < 8) v = S.troot[r];
-                else if ((r -= 8) < 8) v = S.croot[r];
-                else if ((r -= 8) < oods) v = S.samples[r];
-                else if ((r -= oods) < 8 * (K + 1)) v = S.roots[r];
-                else if ((r -= 8 * (K + 1)) < 4) v = S.last[r];
-                else v = S.nonce[r - 4];
-                rec[w] = v;
-            }
+            const uint32_t kinds = K + 3, head = record_head_words(N, K), per_q = N + kCp + 16 * L;
+            const RecordHead hd = {A.const_root, S.troot, S.croot, S.samples, S.roots, S.last, S.nonce};
+            for (uint32_t w = t; w < head; w += kNT) rec[w] = record_head_word(w, hd, N, K);
             uint32_t *plen = rec + stwo_record_words(N, L, Q, K) - (uint64_t)kinds * Q;
-            for (uint32_t i = t; i < kinds * Q; i += kNT) {
-                const uint32_t kind = i / Q;
-                plen[i] = kind < 2 ? L : L + 1 - kind;
-            }
+            for (uint32_t i = t; i < kinds * Q; i += kNT) plen[i] = record_path_len(i, L, Q);
+            // The chains are record_chain (ss_prover_dev.h) on 32-bit rows and the slot's own pointers, written out: through
+            // an ss_p_tree and 64-bit rows the Blake2s instance takes 236 VGPRs where this takes 233.
             for (uint32_t chain = wave; chain < kinds * Q; chain += kWaves) {
                 const uint32_t kind = chain / Q, q = chain - kind * Q, idx = S.queries[q];
                 const uint32_t *levels, *leaf = nullptr;
@@ -872,6 +588,6 @@ extern "C" int ss_p_prove_small_dev(ss_ctx *ctx, const ss_stwo_cfg *cfg, uint64_
         hipLaunchKernelGGL(p_prove_small_kernel<1>, dim3((unsigned)n_groups), dim3(kNT), 0, (hipStream_t)stream, a);
     else
         hipLaunchKernelGGL(p_prove_small_kernel<0>, dim3((unsigned)n_groups), dim3(kNT), 0, (hipStream_t)stream, a);
-    PS_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }

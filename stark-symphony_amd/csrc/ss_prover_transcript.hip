@@ -7,66 +7,16 @@
 // All arithmetic is exact M31 / QM31 on canonical words, so any evaluation order gives the bits of the host route.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-
 #include "../../include/ss_prover.h"
-#include "ss_channel.h"
 #include "ss_ctx.h"
-#include "ss_fields.h"
-#include "ss_hash.h"
-#include "ss_layout.h"
+#include "ss_prover_dev.h"
 
 using namespace ss;
 
 extern "C" int ss_internal_set_err(int code, const char *msg);
 
-#define PT_TRY(expr)                                                                 \
-    do {                                                                             \
-        hipError_t e_ = (expr);                                                      \
-        if (e_ != hipSuccess) {                                                      \
-            char buf_[256];                                                          \
-            snprintf(buf_, sizeof buf_, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            return ss_internal_set_err(SS_ERR_HIP, buf_);                            \
-        }                                                                            \
-    } while (0)
-
 namespace ss {
 namespace {
-
-__device__ __forceinline__ QM31 ldq(const uint32_t *p) { return QM31{p[0], p[1], p[2], p[3]}; }
-__device__ __forceinline__ void stq(uint32_t *p, QM31 v) { p[0] = v.a; p[1] = v.b; p[2] = v.c; p[3] = v.d; }
-__device__ __forceinline__ QM31 ldq16(const uint32_t *p)  // (16-byte aligned)
-{
-    const uint4 v = *reinterpret_cast<const uint4 *>(p);
-    return QM31{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ QM31 qm31_add_c(QM31 x, QM31 y)
-{
-    return {m31_add_c(x.a, y.a), m31_add_c(x.b, y.b), m31_add_c(x.c, y.c), m31_add_c(x.d, y.d)};
-}
-__device__ __forceinline__ QM31 q_shfl_down(QM31 v, uint32_t d)
-{
-    return {__shfl_down(v.a, d, 64), __shfl_down(v.b, d, 64), __shfl_down(v.c, d, 64), __shfl_down(v.d, d, 64)};
-}
-__device__ __forceinline__ QM31 q_shfl_up(QM31 v, uint32_t d)
-{
-    return {__shfl_up(v.a, d, 64), __shfl_up(v.b, d, 64), __shfl_up(v.c, d, 64), __shfl_up(v.d, d, 64)};
-}
-
-template <int HF>
-__device__ __forceinline__ void channel_load(Channel<HF> &ch, const uint32_t *state)
-{
-#pragma unroll
-    for (int i = 0; i < 8; i++) ch.dig.v[i] = Hasher<HF>::native(state[i]);
-    ch.ctr = state[8];
-}
-template <int HF>
-__device__ __forceinline__ void channel_store(const Channel<HF> &ch, uint32_t *state)
-{
-#pragma unroll
-    for (int i = 0; i < 8; i++) state[i] = Hasher<HF>::native(ch.dig.v[i]);
-    state[8] = ch.ctr;
-}
 
 // ------------------------------------------------------------------------ 1. begin: roots, cp_alpha
 // evals_commit (evals/commit.simf:20-35) by one lane: two mixes and a draw are three to four dependent compressions.
@@ -88,8 +38,7 @@ __global__ void p_channel_begin_kernel(Dig const_root, const uint32_t *__restric
 }
 
 // ------------------------------------------------------------------------ 3. OODS point and fold factors
-// One lane: mix the composition root, channel_draw_qm31_point (channel.simf:143-151), then the factor chains
-// x -> pi(x) = 2 x^2 - 1 of P (behind y) and of 2P (no y: the composition columns are held compact).
+// One lane runs oods_point (ss_prover_dev.h).
 template <int HF>
 __global__ void p_oods_point_kernel(uint32_t trace_log, uint32_t *__restrict__ state, const uint32_t *__restrict__ cp_root,
                                     uint32_t *__restrict__ points, uint32_t *__restrict__ fp, uint32_t *__restrict__ f2p,
@@ -100,20 +49,7 @@ __global__ void p_oods_point_kernel(uint32_t trace_log, uint32_t *__restrict__ s
     channel_load(ch, state);
     uint32_t r[8];
     for (int i = 0; i < 8; i++) r[i] = cp_root[i];
-    ch.mix(r);
-    QM31 t, inv;
-    bool ok = ch.draw_qm31(t);
-    const QM31 t_sq = qm31_mul(t, t);
-    ok &= qm31_inv(qm31_add(qm31_one(), t_sq), inv);
-    if (!ok) atomicOr(err, SS_P_ERR_TRANSCRIPT);
-    const QM31 px = qm31_mul(qm31_sub(qm31_one(), t_sq), inv), py = qm31_mul(qm31_add(t, t), inv);
-    const QM31 p2x = qm31_dbl_x(px), pxy = qm31_mul(px, py), p2y = qm31_add(pxy, pxy);
-    stq(points, px); stq(points + 4, py); stq(points + 8, p2x); stq(points + 12, p2y);
-    stq(fp, py);
-    QM31 cur = px;
-    for (uint32_t i = 1; i < trace_log; i++) { stq(fp + 4 * i, cur); cur = qm31_dbl_x(cur); }
-    cur = p2x;
-    for (uint32_t i = 0; i + 1 < trace_log; i++) { stq(f2p + 4 * i, cur); cur = qm31_dbl_x(cur); }
+    if (!oods_point<HF>(ch, r, trace_log, true, points, fp, f2p)) atomicOr(err, SS_P_ERR_TRANSCRIPT);
     channel_store(ch, state);
 }
 
@@ -137,8 +73,6 @@ __global__ void p_oods_point_kernel(uint32_t trace_log, uint32_t *__restrict__ s
 constexpr uint32_t kEvalT = SS_P_EVAL_TILE_LOG, kEvalThreads = 256, kEvalPerLane = 16;
 static_assert(kEvalThreads * kEvalPerLane == 1u << kEvalT, "a lane holds 16 elements of the tile");
 
-__device__ __forceinline__ QM31 fold_q(QM31 even, QM31 odd, QM31 f) { return qm31_add_c(even, qm31_mul_c(odd, f)); }
-
 template <bool QIN>
 __global__ void __launch_bounds__(kEvalThreads)
 p_eval_tile_kernel(uint32_t lv, const uint32_t *__restrict__ in, size_t in_stride, const uint32_t *__restrict__ factors,
@@ -146,15 +80,17 @@ p_eval_tile_kernel(uint32_t lv, const uint32_t *__restrict__ in, size_t in_strid
 {
     __shared__ QM31 s_wave[kEvalThreads / 64];
     const uint32_t tid = threadIdx.x, n_tile = 1u << lv, e0 = tid * kEvalPerLane;
-    const QM31 f0 = ldq(factors);  // (factor addresses do not depend on the lane: uniform loads)
-    QM31 v[8];
+    QM31 r;  // (factor addresses do not depend on the lane: uniform loads)
     if (QIN) {
+        const QM31 f0 = ldq(factors);
         const uint32_t *src = in + (size_t)blockIdx.y * in_stride + (((size_t)blockIdx.x << lv) + e0) * 4;
+        QM31 v[8];
 #pragma unroll
         for (uint32_t j = 0; j < 8; j++) {
             const bool live = e0 + 2 * j + 1 < n_tile;  // n_tile is even: a pair is inside or outside as a whole
-            v[j] = live ? fold_q(ldq16(src + 8 * j), ldq16(src + 8 * j + 4), f0) : qm31_zero();
+            v[j] = live ? fold_q(ldq4(src + 8 * j), ldq4(src + 8 * j + 4), f0) : qm31_zero();
         }
+        r = eval_fold8(v, factors, lv);
     } else {
         const uint32_t *src = in + (size_t)blockIdx.y * in_stride + ((size_t)blockIdx.x << lv) + e0;
         uint32_t c[kEvalPerLane];
@@ -168,34 +104,13 @@ p_eval_tile_kernel(uint32_t lv, const uint32_t *__restrict__ in, size_t in_strid
 #pragma unroll
             for (uint32_t k = 0; k < kEvalPerLane; k++) c[k] = e0 + k < n_tile ? src[k] : 0u;
         }
-#pragma unroll
-        for (uint32_t j = 0; j < 8; j++) {
-            const uint32_t o = c[2 * j + 1];
-            v[j] = QM31{m31_add_c(m31_mul_c(f0.a, o), c[2 * j]), m31_mul_c(f0.b, o), m31_mul_c(f0.c, o), m31_mul_c(f0.d, o)};
-        }
+        r = eval_fold16(c, factors, lv);
     }
-#pragma unroll
-    for (uint32_t s = 1; s < 4; s++) {
-        if (s < lv) {
-            const QM31 f = ldq(factors + 4 * s);
-#pragma unroll
-            for (uint32_t j = 0; j < (8u >> s); j++) v[j] = fold_q(v[2 * j], v[2 * j + 1], f);
-        }
-    }
-    QM31 r = v[0];
-#pragma unroll
-    for (uint32_t s = 0; s < 6; s++) {
-        if (4 + s < lv) r = fold_q(r, q_shfl_down(r, 1u << s), ldq(factors + 4 * (4 + s)));
-    }
+    r = eval_fold_wave(r, factors, lv);
     if ((tid & 63) == 0) s_wave[tid >> 6] = r;
     __syncthreads();
     if (tid) return;
-    if (lv > 10) {
-        const QM31 f10 = ldq(factors + 40);
-        r = fold_q(r, s_wave[1], f10);
-        if (lv > 11) r = fold_q(r, fold_q(s_wave[2], s_wave[3], f10), ldq(factors + 44));
-    }
-    stq(out + (size_t)blockIdx.y * out_stride + 4 * (size_t)blockIdx.x, r);
+    stq(out + (size_t)blockIdx.y * out_stride + 4 * (size_t)blockIdx.x, eval_fold_waves(r, s_wave, factors, lv));
 }
 
 // ------------------------------------------------------------------------ 5. deep_alpha and the DEEP coefficients
@@ -210,17 +125,6 @@ p_eval_tile_kernel(uint32_t lv, const uint32_t *__restrict__ in, size_t in_strid
 // lane 15's power is alpha^16.  The sums A = sum a_k and C = sum c_k are workgroup reductions (__shfl_down, then LDS).
 constexpr uint32_t kDeepThreads = 256;
 
-// deep/quotients.simf:25-36 on canonical values: a0 = -2 Im(v) u, b0 = -2 Im(y) u, c0 = b0 v - a0 y, times alpha^i
-__device__ __forceinline__ void deep_interpolant(QM31 sp_y, QM31 v, QM31 alpha_i, QM31 &a, QM31 &b, QM31 &c)
-{
-    auto neg2 = [](uint32_t x) { return m31_sub_c(0, m31_add_c(x, x)); };
-    const CM31 a0 = {neg2(v.c), neg2(v.d)}, b0 = {neg2(sp_y.c), neg2(sp_y.d)};
-    const QM31 c0 = qm31_sub(qm31_mul_im_c(v, b0), qm31_mul_im_c(sp_y, a0));
-    a = qm31_mul_im_c(alpha_i, a0);
-    b = qm31_mul_im_c(alpha_i, b0);
-    c = qm31_mul_c(alpha_i, c0);
-}
-
 template <int HF>
 __global__ void __launch_bounds__(kDeepThreads)
 p_deep_coeffs_kernel(uint32_t N, uint32_t *__restrict__ state, const uint32_t *__restrict__ samples,
@@ -234,16 +138,7 @@ p_deep_coeffs_kernel(uint32_t N, uint32_t *__restrict__ state, const uint32_t *_
     if (wave == 0) {
         Channel<HF> ch;
         channel_load(ch, state);
-        const uint32_t total = 8 + 4 * (N + kCp), nblk = Hasher<HF>::n_blocks(total);
-        Dig st;
-        Hasher<HF>::iv(st.v);
-        for (uint32_t blk = 0; blk < nblk; blk++) {
-            W16 w;
-            Hasher<HF>::fill(w, blk, nblk, total, ch.dig.v, [&](int, uint32_t i) { return samples[i]; });
-            Hasher<HF>::compress(st, w, blk, nblk, total);
-        }
-        ch.dig = st;
-        ch.ctr = 0;
+        mix_stream<HF>(ch, samples, 4 * (N + kCp), CompressInline<HF>());
         QM31 drawn;
         const bool ok = ch.draw_qm31(drawn);
         if (tid == 0) {  // (every lane of this wavefront has read `state`: they run in lockstep, the loads come first)
@@ -254,12 +149,7 @@ p_deep_coeffs_kernel(uint32_t N, uint32_t *__restrict__ state, const uint32_t *_
     }
     __syncthreads();
     // ---- pw = alpha^(tid + 1)
-    QM31 pw = s_alpha;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const QM31 below = q_shfl_up(pw, d);
-        if (lane >= d) pw = qm31_mul_c(pw, below);
-    }
+    QM31 pw = alpha_powers(s_alpha, lane);
     if (lane == 63) s_total[wave] = pw;
     __syncthreads();
     for (uint32_t w = 0; w < wave; w++) pw = qm31_mul_c(pw, s_total[w]);
@@ -268,11 +158,7 @@ p_deep_coeffs_kernel(uint32_t N, uint32_t *__restrict__ state, const uint32_t *_
     const QM31 step = s_step;
     // the sums of a batch over the workgroup -> sums_out[0..4) = A, [4..8) = C
     auto reduce = [&](uint32_t batch, QM31 A, QM31 C, uint32_t *sums_out) {
-#pragma unroll
-        for (uint32_t d = 32; d; d >>= 1) {
-            A = qm31_add_c(A, q_shfl_down(A, d));
-            C = qm31_add_c(C, q_shfl_down(C, d));
-        }
+        wave_sum2(A, C);
         if (lane == 0) { s_sum[batch][0][wave] = A; s_sum[batch][1][wave] = C; }
         __syncthreads();
         if (tid < 2) {
@@ -326,7 +212,7 @@ extern "C" int ss_p_channel_begin_dev(ss_ctx *ctx, uint32_t hash, const uint32_t
     };
     if (hash) launch(p_channel_begin_kernel<1>);
     else launch(p_channel_begin_kernel<0>);
-    PT_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -344,7 +230,7 @@ extern "C" int ss_p_oods_point_dev(ss_ctx *ctx, uint32_t hash, uint32_t trace_lo
     };
     if (hash) launch(p_oods_point_kernel<1>);
     else launch(p_oods_point_kernel<0>);
-    PT_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -385,7 +271,7 @@ extern "C" int ss_p_eval_at_point_dev(ss_ctx *ctx, uint32_t m, uint32_t ncols, c
         rem -= lv;
         qin = true;
     }
-    PT_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -403,6 +289,6 @@ extern "C" int ss_p_deep_coeffs_dev(ss_ctx *ctx, uint32_t hash, uint32_t n_cols,
     };
     if (hash) launch(p_deep_coeffs_kernel<1>);
     else launch(p_deep_coeffs_kernel<0>);
-    PT_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }

@@ -126,18 +126,12 @@ __global__ __launch_bounds__(256) void p101_fold_kernel(uint32_t layer, uint32_t
 
 using namespace ss;
 
-#define P101_TRY(expr)                                                           \
-    do {                                                                         \
-        hipError_t e_ = (expr);                                                  \
-        if (e_ != hipSuccess) return ss_internal_set_err(SS_ERR_HIP, hipGetErrorString(e_)); \
-    } while (0)
-
 extern "C" int ss_p101_trace_poly(ss_ctx *ctx, uint32_t seed, uint32_t *trace_out, uint32_t *coef_out, void *stream)
 {
     SS_DEVICE_GUARD(ctx);
     if (!trace_out || !coef_out) return ss_internal_set_err(SS_ERR_ARG, "ss_p101_trace_poly: null pointer");
     hipLaunchKernelGGL(p101_trace_poly_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, seed, trace_out, coef_out);
-    P101_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -146,7 +140,7 @@ extern "C" int ss_p101_lde(ss_ctx *ctx, const uint32_t *coef, uint32_t *out, voi
     SS_DEVICE_GUARD(ctx);
     if (!coef || !out) return ss_internal_set_err(SS_ERR_ARG, "ss_p101_lde: null pointer");
     hipLaunchKernelGGL(p101_lde_kernel, dim3((1u << kLdeLog) / 256), dim3(256), 0, (hipStream_t)stream, coef, out);
-    P101_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -157,7 +151,7 @@ extern "C" int ss_p101_composition(ss_ctx *ctx, const uint32_t *p_ev, const uint
     if (!p_ev || !alphas || !out) return ss_internal_set_err(SS_ERR_ARG, "ss_p101_composition: null pointer");
     hipLaunchKernelGGL(p101_composition_kernel, dim3((1u << kLdeLog) / 256), dim3(256), 0, (hipStream_t)stream, p_ev,
                        alphas[0], alphas[1], alphas[2], claim, out);
-    P101_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }
 
@@ -170,6 +164,6 @@ extern "C" int ss_p101_fold(ss_ctx *ctx, uint32_t layer, uint32_t len, uint32_t 
     const uint32_t half = len / 2;
     hipLaunchKernelGGL(p101_fold_kernel, dim3((half + 255) / 256), dim3(256), 0, (hipStream_t)stream, layer, half,
                        beta, in, out);
-    P101_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return SS_OK;
 }

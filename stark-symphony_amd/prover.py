@@ -200,6 +200,29 @@ class GpuProver:
     def _q(v: Q4):
         return (C.c_uint32 * 4)(*[int(x) for x in v])
 
+    @staticmethod
+    def _root_words(root: bytes):
+        """A 32-byte root as the eight uint32 words the library takes."""
+        return (C.c_uint32 * 8)(*np.frombuffer(root, dtype=">u4"))
+
+    @staticmethod
+    def _raise_errors(bits) -> None:
+        """The SS_P_ERR_* bits of one proof, or of a batch, that have no other route: raises what prove_proof raises."""
+        bits = np.asarray(bits)
+        if (bits & 4).any():  # SS_P_ERR_TRANSCRIPT
+            raise AssertionError("transcript: a draw ran out of tries, or 1 + t^2 has no inverse")
+        if (bits & 1).any():  # SS_P_ERR_LAST_LAYER
+            raise AssertionError("last FRI layer is not constant: the quotient is not low degree")
+
+    def _set_timings(self, marks, t_start: float) -> None:
+        """timings <- the time between consecutive marks, by name, and their total."""
+        prev = t_start
+        self.timings = {}
+        for name, ts in marks:
+            self.timings[name] = ts - prev
+            prev = ts
+        self.timings["total"] = prev - t_start
+
     def _call(self, name: str, *args) -> None:
         B.check(getattr(self.lib, name)(self.ver.ctx, *args, self._stream()))
 
@@ -348,7 +371,7 @@ class GpuProver:
             # channel[9], cp_alpha[4], points[16], sums + alpha^16 [20], fold factors of P [n][4] and of 2P [n - 1][4]
             tr = self._empty(52 + 8 * n)
             state, cp_alpha_dev, points, sums, fac = tr[:9], tr[12:16], tr[16:32], tr[32:52], tr[52:]
-            self._call("ss_p_channel_begin_dev", hsel, (C.c_uint32 * 8)(*np.frombuffer(const_root, dtype=">u4")),
+            self._call("ss_p_channel_begin_dev", hsel, self._root_words(const_root),
                        trace_tree[2 * size_L - 2].data_ptr(), state.data_ptr(), cp_alpha_dev.data_ptr(), err.data_ptr())
         else:
             trace_root = self._root(trace_tree, size_L)
@@ -624,12 +647,7 @@ class GpuProver:
             np.stack([got[ks].reshape(Q, 4) for ks, _ in k_layers]),
             [list(hashes(got[kh], Q, L - 1 - l)) for l, (_, kh) in enumerate(k_layers)], nonce)
         mark("decommit")
-        prev = t_start
-        self.timings = {}
-        for name, ts in marks:
-            self.timings[name] = ts - prev
-            prev = ts
-        self.timings["total"] = prev - t_start
+        self._set_timings(marks, t_start)
         return proof
 
     # -- the proof as the verifier's record, in device memory ------------------------------------
@@ -647,7 +665,7 @@ class GpuProver:
         trees_dev = self.torch.tensor([[t.data_ptr() if t is not None else 0 for t in row] for row in desc], dtype=self.torch.int64)
         # (device transcript: from pinned memory, so that the upload does not wait for the stream)
         trees_dev = trees_dev.pin_memory().to(self.dev, non_blocking=True) if c.on_dev else trees_dev.to(self.dev)
-        root = (C.c_uint32 * 8)(*np.frombuffer(c.const_root, dtype=">u4").astype(np.uint32))
+        root = self._root_words(c.const_root)
         args = (C.byref(c.cs), trees_dev.data_ptr(), c.samples.data_ptr(), c.roots_dev.data_ptr(), c.last.data_ptr(),
                 nonce_dev.data_ptr(), root, queries_dev.data_ptr(), out.data_ptr())
         if words_out is None:
@@ -736,10 +754,7 @@ class GpuProver:
             bits = int(err.cpu()[0])
         else:
             bits, self.record_words = (int(x) for x in self.torch.cat([err, words.reshape(1)]).cpu())
-        if bits & 4:  # SS_P_ERR_TRANSCRIPT
-            raise AssertionError("transcript: a draw ran out of tries, or 1 + t^2 has no inverse")
-        if bits & 1:
-            raise AssertionError("last FRI layer is not constant: the quotient is not low degree")
+        self._raise_errors(bits)
         if bits & 2:
             _, _, nonce, queries = self._host_tail(c)
             tail = self.torch.from_numpy(np.array(queries + [nonce >> 32, nonce & 0xFFFFFFFF], dtype=np.uint32).view(np.int32)).to(self.dev)
@@ -751,12 +766,7 @@ class GpuProver:
             self.timings = {"total": time.perf_counter() - c.t_start}
             return
         c.mark("tail")
-        prev = c.t_start
-        self.timings = {}
-        for name, ts in c.marks:
-            self.timings[name] = ts - prev
-            prev = ts
-        self.timings["total"] = prev - c.t_start
+        self._set_timings(c.marks, c.t_start)
 
     def prove_records(self, seeds: Sequence[int], workers: int = 4, one_launch: bool = False, n_groups: int = 0, **kw):
         """prove_record for every seed of `seeds` (keywords, transcript= included, are passed on) on the schedule of
@@ -812,17 +822,14 @@ class GpuProver:
         arena_words = self.lib.ss_p_small_arena_words(C.byref(cs), n_groups)
         (_, itw_n, _), (tw_c, itw_c, hxhy_c), (tw_l, itw_l, hxhy_l) = self.domain(trace_log), self.domain(trace_log + 1), self.domain(L)
         tables = SmallTables(*[x.data_ptr() for x in (itw_n, tw_c, itw_c, hxhy_c, tw_l, itw_l, hxhy_l)])
-        root = (C.c_uint32 * 8)(*np.frombuffer(HASHES[hash](b"").digest(), dtype=">u4"))
+        root = self._root_words(HASHES[hash](b"").digest())
         seeds_dev = torch.tensor(seeds, dtype=torch.int64).pin_memory().to(self.dev, non_blocking=True)
         arena, rows, err = self._empty(arena_words), self._empty(n, words), self._empty(n)
         span = pow_span if pow_span is not None else 1 << min(22, pow_bits + 8)
         self._call("ss_p_prove_small_dev", C.byref(cs), cs.pow_target, span, seeds_dev.data_ptr(), n, n_groups, C.byref(tables),
                    root, arena.data_ptr(), arena_words, rows.data_ptr(), words, err.data_ptr())
         self.small_errors = bits = self._host(err).copy()  # the one read: it waits for the launch
-        if (bits & 4).any():
-            raise AssertionError("transcript: a draw ran out of tries, or 1 + t^2 has no inverse")
-        if (bits & 1).any():
-            raise AssertionError("last FRI layer is not constant: the quotient is not low degree")
+        self._raise_errors(bits)
         for i in np.flatnonzero(bits & 2):  # no nonce in the span: the existing route, whose check() searches on
             self.prove_record(out=rows[int(i)], seed=seeds[int(i)], pow_span=span, transcript="device", **shape)
         dt = time.perf_counter() - t0

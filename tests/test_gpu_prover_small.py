@@ -79,6 +79,19 @@ def test_rows_equal_the_numpy_provers(gp, case):
     assert np.array_equal(gp.prove_records(seeds, one_launch=True, **CASES[case][0]).cpu().numpy().view(np.uint32), want)
 
 
+def test_two_columns_have_no_constraint(gp):
+    """n_cols = 2: trace_row stores its second column and never enters its recurrence, and composition_point reads two
+    columns and sums no constraint (the composition polynomial is zero).  The one-launch rows against the launch chain
+    of prove_record on the device transcript, which calls the same steps from its grid kernels, and against the numpy prover."""
+    kw = dict(n_cols=2, trace_log=2, log_blowup=1, n_queries=2, pow_bits=1)
+    seeds = [0, 1, 2]
+    want = np.stack([verifier.stwo_record(ss.stwo_from_json(stwo_prover.prove(seed=s, **kw))) for s in seeds])
+    rc, got, err = launch(gp, kw, seeds)
+    assert rc == 0 and not err.any() and np.array_equal(got, want)
+    for i, s in enumerate(seeds):
+        assert np.array_equal(got[i], gp.prove_record(seed=s, transcript="device", **kw).cpu().numpy().view(np.uint32)), s
+
+
 def test_a_slot_is_reused_from_proof_to_proof(gp):
     rc, got, err = launch(gp, TEST_JSON, range(5), n_groups=2)
     assert rc == 0 and not err.any() and len({r.tobytes() for r in got}) == 5
