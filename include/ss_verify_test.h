@@ -61,7 +61,10 @@ int ss_stwo_ws_layout_of(const ss_stwo_cfg *cfg, size_t n, ss_stwo_ws_layout *ou
  *         x+y, x-y, x*y, and (a[1] * 2^32 + b[1]) mod P)
  *   op 6  the asserts behind the FRI layer loop as the query kernel evaluates them (fri/verify.simf:124-128,
  *         fri/layers.simf:73-78): in (mode, lde_log, n_layers, query, folded position, folded value[4], last layer[4])
- *         -> out the first failing status code, 0 = none (stages 8 / 9 of the stwo status codes)            */
+ *         -> out the first failing status code, 0 = none (stages 8 / 9 of the stwo status codes)
+ *   op 7  channel_draw_qm31 (channel.simf:115-140) as the prover kernels call it, one draw: in (hash 0 SHA-256 | 1 Blake2s,
+ *         digest[8] stored words, counter) -> out (1 or 0 after 256 refused attempts, drawn[4], counter afterwards); a hash
+ *         above 1 is taken as 1                                                                              */
 int ss_selftest(ss_ctx *ctx, int op, size_t n, const uint32_t *in_host, uint32_t *out_host);
 
 /* Device replay of the reference's known-answer tests -- the `fn test_...` bodies of every .simf file under stark101/src and

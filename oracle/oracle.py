@@ -227,6 +227,20 @@ def qm_array(vals: Sequence[Sequence[int]]):
     return arr
 
 
+def channel_draw_qm31(digest: bytes, counter: int, hash: str = "sha256"):
+    """-> (rc, the four drawn words, the counter afterwards): so_channel_draw_qm31 (channel.simf:115-140) on a given state."""
+    ch, q = Channel(), QM31()
+    C.memmove(ch.digest, digest, 32)
+    ch.counter = counter
+    L = lib()
+    L.so_set_hash(1 if hash == "blake2s" else 0)
+    try:
+        rc = L.so_channel_draw_qm31(C.byref(ch), C.byref(q))
+    finally:
+        L.so_set_hash(0)
+    return int(rc), q.t(), int(ch.counter)
+
+
 # ------------------------------------------------------------------------- stark101
 def _fill_eval(dst: S101Eval, ev) -> None:
     dst.ev = ev.ev

@@ -12,6 +12,7 @@
 #include <string>
 
 #include "ss_abi.h"
+#include "ss_channel.h"
 #include "ss_copy.h"
 #include "ss_ctx.h"
 #include "ss_fields.h"
@@ -1098,6 +1099,19 @@ extern "C" int ss_s101_verify_files(ss_ctx *ctx, size_t n, const char *const *pa
 
 // =========================================================================== self-test
 namespace ss {
+// x = stored digest words [8], counter -> o = ok, the four drawn words, the counter afterwards
+template <int HF>
+__device__ void selftest_draw(const uint32_t *x, uint32_t *o)
+{
+    Channel<HF> c;
+    for (int j = 0; j < 8; j++) c.dig.v[j] = Hasher<HF>::native(x[j]);
+    c.ctr = x[8];
+    QM31 q;
+    o[0] = c.draw_qm31(q) ? 1 : 0;
+    o[1] = q.a; o[2] = q.b; o[3] = q.c; o[4] = q.d;
+    o[5] = c.ctr;
+}
+
 __global__ void selftest_kernel(int op, uint32_t n, const uint32_t *in, uint32_t *out)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1162,14 +1176,21 @@ __global__ void selftest_kernel(int op, uint32_t n, const uint32_t *in, uint32_t
         out[i] = c == 0xffffffffu ? 0 : c;
         break;
     }
+    case 7: {  // channel_draw_qm31 (channel.simf:115-140) as every prover kernel calls it: Channel<HF>::draw_qm31
+        const uint32_t *x = in + 10 * i;
+        uint32_t *o = out + 6 * i;
+        if (x[0] == 0) selftest_draw<0>(x + 1, o);
+        else selftest_draw<1>(x + 1, o);
+        break;
+    }
     }
 }
 }  // namespace ss
 
 extern "C" int ss_selftest(ss_ctx *ctx, int op, size_t n, const uint32_t *in_host, uint32_t *out_host)
 {
-    static const int in_w[7] = {16, 2, 8, 1, 2, 8, 13}, out_w[7] = {8, 4, 8, 2, 4, 16, 1};
-    if (!ctx || !in_host || !out_host || op < 0 || op > 6 || !n) return set_err(SS_ERR_ARG, "bad argument");
+    static const int in_w[8] = {16, 2, 8, 1, 2, 8, 13, 10}, out_w[8] = {8, 4, 8, 2, 4, 16, 1, 6};
+    if (!ctx || !in_host || !out_host || op < 0 || op > 7 || !n) return set_err(SS_ERR_ARG, "bad argument");
     std::lock_guard<std::mutex> lock(ctx->mu);
     SS_DEVICE_GUARD(ctx);
     DevBuf a, b;
